@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- SWEM 480p multi-object inference throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -274,6 +274,19 @@ def cpu_baseline(frames, m0, sd, n_frames=20, warm=2):
                       '(one per physical core available; %s)' % (warm, n_frames, dt, threads, cpu['model'])}
 
 
+def dump_outputs(path, outs, limit=64 * 10 ** 6 - 4096):
+    """--dump-outputs: the int64 index maps one timed step returned (one (H, W) map per sequence, in sequence order) as
+    path/index_maps.npy, float32 of shape (sequences, H, W); above `limit` bytes a fixed seeded sample of its values (flat).
+    (The limit leaves room for the .npy header: the file stays within 64 MB.)"""
+    import numpy as np
+    maps = torch.cat([o.reshape((-1,) + tuple(o.shape[-2:])) for o in outs]).cpu().numpy().astype(np.float32)
+    if maps.nbytes > limit:
+        keep = np.sort(np.random.default_rng(0).choice(maps.size, limit // maps.itemsize, replace=False))
+        maps = maps.reshape(-1)[keep]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'index_maps.npy'), maps)
+
+
 def training_leg(cpu=True, steps=10):
     """BASELINE configs C / D (the training step, reference swem_trainer.py:59-108): a short leg of tools/train_bench.py -- 4 clips of
     3 x 384x384, 2 objects, ResNet-50, K = 256, graph replay, the shipped training plans -- in a CHILD process (its own trainer,
@@ -313,9 +326,15 @@ def main():
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--regions', type=int, default=7,
-                    help='how many times the timed region of --steps steps is run back to back (each bracketed by barrier + '
-                         'synchronize, max over ranks): `value` is the MEDIAN region, value_min / value_max the spread (one region '
-                         'of 20 steps is 0.17 s: box-to-box and run-to-run noise of +-4 %% otherwise decides the line)')
+                    help='into how many back-to-back regions the --steps timed steps are split (each a whole number of graph '
+                         'replays, bracketed by barrier + synchronize, max over ranks; fewer when --steps holds fewer replays): '
+                         '`value` is the MEDIAN region, value_min / value_max the spread (one region of 20 steps is 0.17 s: '
+                         'box-to-box and run-to-run noise of +-4 %% otherwise decides the line)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last one returned -- the index map of every sequence of rank 0, '
+                         'in sequence order -- to DIR/index_maps.npy (float32; above 64 MB a fixed seeded sample of its pixels).  '
+                         'Two runs compute with the same plans where the line\'s plans.digest agrees: shapes missing from the '
+                         'shipped plan file are tuned by timing during warm-up, --load-plans FILE fixes them all')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--objects', type=int, default=N_OBJ)
     ap.add_argument('--no-autotune', action='store_true')
@@ -328,7 +347,8 @@ def main():
     ap.add_argument('--lookahead', type=int, default=-1,
                     help='frames per graph replay with the key encoder batched over them (evaluator.LookaheadGraph); 0 = one frame '
                          'per replay; default: the divisor of --steps nearest to 8 (the timed region then holds exactly --steps '
-                         'frames per sequence: 10 for 20 or 100 steps, 8 for 24 / 40 / 48), else 4')
+                         'frames per sequence: 10 for 20 or 100 steps, 8 for 24 / 40 / 48), else 4 (then the last region also runs '
+                         'the rest of a replay it does not count); a value given here must divide --steps')
     ap.add_argument('--seqs', type=int, default=8,
                     help='sequences in flight per GPU (default 8 = two lock-step lanes of four; round 5: --seqs 4 --lockstep 0)')
     ap.add_argument('--lockstep', type=int, default=4,
@@ -352,6 +372,11 @@ def main():
     ap.add_argument('--object-legs', type=int, nargs='*', default=[1, 3],
                     help='extra single-sequence legs at these object counts, both arithmetics (default 1 3; empty: none)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.lookahead > 0 and args.steps % args.lookahead:
+        ap.error('--lookahead %d does not divide --steps %d: a timed region would replay frames it does not count'
+                 % (args.lookahead, args.steps))
     if args.lookahead < 0:
         # a longer look-ahead batches the key encoder further (8-10 frames: + 2-3 % over 4, profiles/r04_lookahead_sweep.txt); the
         # replay granularity must divide the timed steps, or the region would hold up to k - 1 frames of work it does not count
@@ -469,19 +494,22 @@ def main():
             sts.append(st)
         return rs, sts
 
+    last_outs = []
+
     def timed(rs, sts, steps):
         """EXACTLY `steps` steps (one frame of every sequence each) between barrier + synchronize; (frames, seconds) over
-        all ranks: total frames, max-over-ranks time."""
+        all ranks: total frames, max-over-ranks time.  What the last step returned is left in `last_outs`."""
         sdist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
             if len(rs) == 1:
-                rs[0].step()
+                outs = [rs[0].step()]
             else:
+                outs = []
                 for rn, st in zip(rs, sts):
                     with torch.cuda.stream(st):
-                        rn.step()
+                        outs.append(rn.step())
         # (the blocking synchronize sleeps on an interrupt; on hosts that deliver it late -- wake-ups quantised to 100 ms were
         # measured here -- the clock would include up to a tick of idle time: poll the streams' events first)
         ops.spin_sync(sts)
@@ -489,16 +517,25 @@ def main():
         elapsed = time.perf_counter() - t0
         ops.check_faults()       # (outside the clock) a K-split / stream-K wait that expired inside the region raises here
         sdist.barrier()
+        last_outs[:] = outs
         return sdist.reduce_counters(steps * sum(getattr(rn, 'nseq', 1) for rn in rs), elapsed, device=dev)
 
     def timed_median(rs, sts, steps):
-        """--regions timed regions back to back -> (frames of one region, the MEDIAN region's seconds, frames/s of every
-        region in run order).  Every region is the contract's: exactly `steps` steps between barrier + synchronize, max over
-        ranks; the median is taken over the regions' max-over-ranks times (every rank computes the same list)."""
-        regs = [timed(rs, sts, steps) for _ in range(max(1, args.regions))]
-        ts = sorted(t for _, t in regs)
+        """EXACTLY `steps` timed steps, split into up to --regions regions back to back -> (frames of the `steps` steps, `steps`
+        x the MEDIAN region's seconds per step, frames/s of every region in run order).  Every region is the contract's: a whole
+        number of graph replays (k steps of a look-ahead / lock-step runner; the last region also takes the steps that do not
+        fill one) between barrier + synchronize, max over ranks; the median is taken over the regions' max-over-ranks times per
+        step (every rank computes the same list)."""
+        r0 = rs[0]
+        k = r0.k if isinstance(r0, LockstepRunner) else (r0.look.k if r0.look is not None else 1)
+        groups = steps // k
+        n = max(1, min(args.regions, groups))
+        sizes = [k * (groups // n + (i < groups % n)) for i in range(n)]
+        sizes[-1] += steps - sum(sizes)
+        regs = [timed(rs, sts, s) for s in sizes]
+        ts = sorted(t / s for (_, t), s in zip(regs, sizes))
         med = ts[len(ts) // 2] if len(ts) % 2 else 0.5 * (ts[len(ts) // 2 - 1] + ts[len(ts) // 2])
-        return regs[0][0], med, [round(f / t, 3) for f, t in regs]
+        return regs[0][0] // sizes[0] * steps, med * steps, [round(f / t, 3) for f, t in regs]
 
     pipelined = args.pipeline == 'on' or (args.pipeline == 'auto' and nseq == 1)
     main_tag, pmc_tag = (), ''
@@ -517,8 +554,10 @@ def main():
         book.save(args.save_plans)
     hist = book.math_histogram(main_tag)
 
-    # ---------------- timed region: exactly K steps between barrier + synchronize, --regions times; the median region counts
+    # ---------------- timed region: exactly K steps in all, as up to --regions regions between barrier + synchronize; the median region counts
     total_frames, max_t, region_fps = timed_median(runners, streams, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outs)
 
     def launch_text(pipe_, lock_=False):
         if args.no_graph:
@@ -549,8 +588,8 @@ def main():
             'ms_per_step': round(1e3 * max_t / args.steps, 3), 'ms_per_frame': round(1e3 * max_t / total_frames * world, 3),
             'timed_regions': len(region_fps), 'value_min': min(region_fps), 'value_max': max(region_fps),
             'value_regions': region_fps,
-            'value_note': 'value = frames of one region of --steps steps / the MEDIAN region time over --regions back-to-back regions '
-                          '(each: barrier + synchronize on both sides, max over ranks); ms_per_step = that median / steps',
+            'value_note': 'the --steps timed steps run as up to --regions back-to-back regions (each: barrier + synchronize on both '
+                          'sides, max over ranks); ms_per_step = the MEDIAN region time per step, value = frames per step / that time',
             'higher_is_better': True, 'scaling': 'weak',
             'vs_baseline': None,
             # what the arithmetic IS (not a precision claim): storage and accumulation are fp32 everywhere, the convolutions'
