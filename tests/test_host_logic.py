@@ -197,6 +197,33 @@ def test_shipped_plan_file_is_well_formed():
     assert isinstance(book.digest(), str) and len(book.digest()) == 12
 
 
+@pytest.mark.parametrize('name,tag', [('mi355x_train_384_k256_amp', ('math', 2)),
+                                      ('mi355x_train_384_k256_fp32_level', ('math', 0, 1, 7))])
+def test_shipped_training_plan_file_is_well_formed(name, tag):
+    """The two training plan files (bench.py's `training` leg): every key a layer signature with the conv_math tag of its
+    arithmetic, flags among those the training step launches (forward with or without input ReLU, data gradient with the EH / EW
+    edge bits or the ReLU mask), and every plan one that resolve_plan (csrc/conv.hip) takes as it is -- a valid tile and K-split,
+    nothing that silently becomes the heuristic -- in an arithmetic the layer really runs: a math field other than 0 needs the
+    pre-split form (Cin % 32 == 0, at most 64 taps), without it the library runs the fp32 kernels whatever the plan says.  The
+    AMP file holds plain bf16 (2) or fp32 (0) only, the fp32-level file never a 16-bit or 8-bit operand mode (2 / 3)."""
+    from swem_amd import ops
+    book = ops.PlanBook().load(ops.shipped_plans(name))
+    assert len(book.conv) >= 50 and not book.match
+    for k, v in book.conv.items():
+        assert len(k) == 10 + len(tag) and tuple(k[10:]) == tag, k
+        cin, cout, kh, kw, stride, pad, flags, B, H, W = k[:10]
+        assert flags in (0, ops.RELU_IN, ops.DGRAD, ops.DGRAD | ops.DGRAD_EH | ops.DGRAD_EW, ops.DGRAD | ops.MASK_POS), k
+        assert cin > 0 and cout % 4 == 0 and kh == kw and stride in (1, 2) and B > 0 and H > 0 and W > 0, k
+        wm, wn, ns, math = v & 15, (v >> 4) & 15, (v >> 8) & 255, (v >> 16) & 7
+        assert math in ((0, 2) if tag == ('math', 2) else (0, 1, 7)), (k, hex(v))
+        if v == 0:
+            continue                   # (the tuner found the library's own heuristic fastest: fp32 MFMA, its tile)
+        presplit = math & 3 != 0
+        t256 = wm == wn == 4 and (v >> 24) & 15 == 0 and (math == 7 or (math == 1 and (v >> 20) & 15 == 4))
+        assert 1 <= ns <= 255 and (t256 or (wm in (1, 2) and wn in (1, 2) and not (wm == 2 and wn == 1 and not presplit))), (k, hex(v))
+        assert math == 0 or (cin % 32 == 0 and kh * kw <= 64), ('a plan in an arithmetic this layer cannot run', k, hex(v))
+
+
 def test_plan_epochs_gate_planes_only_outputs(tmp_path):
     """ops.PlanBook.epoch(): the count a planes-only convolution output depends on (ops.conv2d(planes_only=True) leaves the fp32
     map out only while its consumer's request for planes carries the CURRENT count).  Every change that can send a consumer down
