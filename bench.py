@@ -1,9 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- SWEM 480p multi-object inference throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline alone: set-up, warm-up, the K timed steps, --dump-outputs, the JSON line.  --full adds
+everything else the line can carry (the objects listed below), each a run of its own after the timed steps.
 
 Workload (BASELINE.json configs[1]): synthetic structured 480x864 clip, ResNet-50 key encoder, ResNet-18 value
 encoder, K=256 bases, 5 EM iterations, 2 objects, output 480x854, random weights of the reference architecture.
@@ -21,7 +24,7 @@ value = frames of all ranks / max-over-ranks time.
 Arithmetic of the line (`dtype`, `plans`): the shipped plans run the convolutions in f16x3 -- operands as fp16 hi + mid pairs
 (22-23 significant bits), three MFMA products, fp32 accumulation: the error of the exact fp32 kernels.
 
-Extra objects in the JSON line:
+Extra objects in the JSON line (--full; the --no-* options below leave some of them out):
   roofline     -- dominant conv kernel of the timed leg: useful conv FLOPs / summed launch durations (HIP events on the launch
                   stream) against ITS pipe's ceiling (dense f16 / bf16 MFMA peak / products per fp32 product); mfma_busy and
                   traffic from the committed rocprofv3 --pmc passes (profiles/r06_conv_pmc*.json, r06_conv_traffic_by_kernel*.json);
@@ -31,6 +34,7 @@ Extra objects in the JSON line:
   single_sequence, objects -- one sequence at a time (the reference's FPS semantics); 1 and 3 objects, both arithmetics.
   em_matching  -- the EM / matching kernels against the fp32 matrix peak (algorithmic and executed FLOPs).
   cpu_baseline -- the CPU oracle (oracle/, a port of the reference's PyTorch path) on the same clip, bounded sample.
+  whole_frame, conv_frac_time_weighted -- from the roofline leg; training -- BASELINE configs C / D (training_leg).
 """
 import argparse
 import json
@@ -335,6 +339,10 @@ def main():
                          'in sequence order -- to DIR/index_maps.npy (float32; above 64 MB a fixed seeded sample of its pixels).  '
                          'Two runs compute with the same plans where the line\'s plans.digest agrees: shapes missing from the '
                          'shipped plan file are tuned by timing during warm-up, --load-plans FILE fixes them all')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every other leg of the line (single sequence, fp32_level, objects, '
+                         'roofline, whole_frame, em_matching, cpu_baseline, training); the --no-* options below leave some out.  '
+                         'Without it the run stops at the headline: set-up, warm-up, timed steps, --dump-outputs, the JSON line')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--objects', type=int, default=N_OBJ)
     ap.add_argument('--no-autotune', action='store_true')
@@ -374,6 +382,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if not args.full and (args.conv_report or args.trace_layers):
+        ap.error('--conv-report and --trace-layers report on the roofline leg: add --full')
     if args.lookahead > 0 and args.steps % args.lookahead:
         ap.error('--lookahead %d does not divide --steps %d: a timed region would replay frames it does not count'
                  % (args.lookahead, args.steps))
@@ -868,7 +878,8 @@ def main():
         del r1, s1
         return d
 
-    if not args.no_legs and world == 1:
+    # (a plain run ends at the headline: every leg below runs with --full only)
+    if args.full and not args.no_legs and world == 1:
         if nseq != 1 and not args.no_graph:
             d1 = single_leg(2234)
             if rank == 0:
@@ -925,7 +936,7 @@ def main():
         if args.save_plans and rank == 0:
             book.save(args.save_plans)             # again: with the plans the extra legs tuned
 
-    if world == 1 and not args.no_roofline:
+    if args.full and world == 1 and not args.no_roofline:
         roof, pipes, per_pipe, peaks, nprof = leg_roofline(runners[0] if lockstep else runner, hist, pmc_tag)
         out['roofline'] = roof
         out['conv_frac_time_weighted'] = roof['frac_time_weighted_all_conv_kernels']    # (beside roofline.frac: VERDICT r05 item 8)
@@ -1065,7 +1076,7 @@ def main():
                           '4PL(C(3T-1)+V) + 4LmP(C+V) per object' % em_streams)
         if not args.no_cpu_baseline and world == 1:     # reported at N = 1 only
             out['cpu_baseline'] = cpu_baseline(frames_cpu, m0_cpu, sd, n_frames=args.cpu_frames)
-    if rank == 0 and world == 1 and not args.no_training and not args.no_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_training and not args.no_legs:
         out['training'] = training_leg(cpu=not args.no_cpu_baseline)
     if rank == 0:
         print(json.dumps(out))

@@ -1053,3 +1053,36 @@ def test_bench_steps_and_dump_outputs(lib, tmp_path):
     assert maps.dtype == np.float32 and maps.shape == (4, 480, 854)
     assert np.array_equal(maps, np.round(maps)) and maps.min() >= 0 and maps.max() <= 2
     assert maps.max() >= 1                           # (not an empty map: some object is predicted somewhere)
+
+
+def test_bench_plain_run_and_full(lib):
+    """A plain `bench.py` run stops at the headline: its line carries none of the other legs' objects.  With --full the same
+    configuration (two lock-step lanes of two sequences) also runs the single-sequence, fp32-level and roofline legs, the EM /
+    matching timing and the CPU baseline, and the line carries each of them (the training record and the extra object counts are
+    left out here: --no-training, --object-legs with no count)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
+    env = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--steps', '4', '--warmup', '2', '--regions', '2', '--lookahead', '2',
+           '--seqs', '4', '--lockstep', '2', '--no-autotune']
+    extras = ('single_sequence', 'fp32_level', 'exact_split_fps', 'value_by_arithmetic', 'objects', 'roofline', 'whole_frame',
+              'em_matching', 'cpu_baseline', 'training')
+    lines = {}
+    for mode, opts in (('plain', []), ('full', ['--full', '--no-training', '--object-legs', '--cpu-frames', '1'])):
+        out = subprocess.run(cmd + opts, env=env, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, (mode, out.stderr[-3000:])
+        lines[mode] = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
+    for d in lines.values():
+        assert d['steps'] == 4 and d['warmup'] == 2 and d['value'] > 0 and d['ms_per_step'] > 0 and d['higher_is_better']
+        assert d['config']['frames_per_step'] == 4 and d['config']['lockstep_lanes'] == 2
+    assert not [k for k in extras if k in lines['plain']], sorted(lines['plain'])
+    full = lines['full']
+    assert [k for k in extras if k in full] == ['single_sequence', 'fp32_level', 'exact_split_fps', 'value_by_arithmetic',
+                                                'roofline', 'whole_frame', 'em_matching', 'cpu_baseline'], sorted(full)
+    assert full['fp32_level']['value'] > 0 and 'roofline' in full['fp32_level'] and full['roofline']['achieved'] > 0
+    assert full['em_matching']['ms_per_frame'] > 0 and full['cpu_baseline']['value'] > 0

@@ -505,3 +505,17 @@ def test_lockstep_host_logic():
     assert re.search(r"add_argument\('--seqs', type=int, default=8", src) and re.search(r"add_argument\('--lockstep', type=int, default=4", src)
     hdr = open(os.path.join(root, 'include', 'swem_hip.h')).read()
     assert 'swem_upsample_add_grouped_nhwc_f32(' in hdr and 'swem_upsample_add_grouped_nhwc_f32_planes(' in hdr
+
+
+def test_bench_extra_legs_need_full():
+    """A plain `bench.py` run measures the headline alone; every other leg (roofline, EM / matching, CPU baseline, the other
+    arithmetics, object counts and the training record) runs behind --full.  The options that only report on the roofline leg
+    refuse a plain run instead of doing nothing (parsed before the bench touches a device)."""
+    import subprocess
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'bench.py')
+    out = subprocess.run([sys.executable, bench, '--help'], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and '--full' in out.stdout, out.stderr[-2000:]
+    for opt in (['--trace-layers', 'layers.json'], ['--conv-report']):
+        out = subprocess.run([sys.executable, bench] + opt, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 2 and 'add --full' in out.stderr, (opt, out.stderr[-2000:])

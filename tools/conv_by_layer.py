@@ -3,7 +3,7 @@
 the rocprofv3 kernel trace of THE SAME RUN, so that every conv layer's TFLOP/s and the per-pipe roofline fractions can be
 recomputed from profiles/ alone.
 
-    rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 bench.py --steps 6 --warmup 2 --no-graph --seqs 1 \
+    rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 bench.py --full --steps 6 --warmup 2 --no-graph --seqs 1 \
         --no-em --no-cpu-baseline --load-plans PLANS --trace-layers OUT/layers.json
     python tools/conv_by_layer.py OUT/layers.json OUT/*/*_kernel_trace.csv profiles/r02_conv_by_layer.csv
 

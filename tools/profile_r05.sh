@@ -6,7 +6,7 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_r05; mkdir -p $OUT
 WHAT="${*:-stats pmc traffic em}"
-COMMON="--no-cpu-baseline --no-em --no-legs"
+COMMON="--full --no-cpu-baseline --no-em --no-legs"
 for leg in default exact; do
   MM=""; TAG=""
   if [ $leg = exact ]; then MM="--math-modes 0 1"; TAG="_exact"; fi
