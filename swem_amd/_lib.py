@@ -1,4 +1,4 @@
-"""ctypes binding of libswem_hip.so (C ABI: include/swem_hip.h).
+"""ctypes binding of libswem_hip.so (C ABI: include/swem_hip.h, swem_hip_train.h, swem_hip_metrics.h).
 
 There is no CPU fallback: if the library is missing or a call fails this module raises.
 Build the library with ``python -m swem_amd.build`` (or ``__graft_entry__.build()``).
@@ -123,6 +123,9 @@ SIGNATURES = {
     'swem_pred_head_bwd_workspace': (_sz, [_i, _i, _i, _i]),
     'swem_pred_head_bwd_f32': (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _sz]),
     'swem_prep_value_input_bwd_f32': (_i, [_p, _p, _p, _i, _i, _i, _i, _i]),
+    # ---- include/swem_hip_metrics.h
+    'swem_jf_workspace': (_sz, [_i, _i, _i, _i]),
+    'swem_jf_counts_u8': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _sz]),
 }
 
 _lib = None
