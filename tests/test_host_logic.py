@@ -519,3 +519,73 @@ def test_bench_extra_legs_need_full():
     for opt in (['--trace-layers', 'layers.json'], ['--conv-report']):
         out = subprocess.run([sys.executable, bench] + opt, capture_output=True, text=True, timeout=300)
         assert out.returncode == 2 and 'add --full' in out.stderr, (opt, out.stderr[-2000:])
+
+
+def _walk_lane(t, k, binds, pipelined):
+    """Drive evaluator.lane_schedule the way the pools' lane loop does, with a graph that always / never binds; returns the
+    steps taken as (action, first frame, number of frames) and the frames at which a bind was attempted."""
+    from swem_amd import evaluator as E
+    steps, tried, i, bound = [], [], 1, False
+    while i < t:
+        act, n = E.lane_schedule(t, k, i, bound, bound and pipelined, True)
+        if act == E.BIND:
+            assert n == 0
+            tried.append(i)
+            bound = binds
+            act, n = E.lane_schedule(t, k, i, bound, bound and pipelined, False)
+        assert act != E.BIND and n >= 1
+        steps.append((act, i, n))
+        if act == E.LAST_GROUP:
+            bound = False
+        i += n
+        assert len(steps) <= t
+    return steps, tried
+
+
+@pytest.mark.parametrize('binds', [True, False])
+def test_lane_schedule_keeps_the_last_frame_out_of_the_graphs(binds):
+    """The group-scheduling rule of SequencePool / LockstepPool (evaluator.lane_schedule) for every sequence length 1..40 and
+    look-ahead 0..12, with a graph that always binds and one that never does: what the pools' lane loop promises."""
+    from swem_amd import evaluator as E
+    graph_acts = (E.GROUP_AND_NEXT, E.LAST_GROUP, E.GRAPH_FRAME)
+    for t in range(1, 41):
+        for k in range(0, 13):
+            for pipelined in ((False, True) if k == 0 else (False,)):
+                steps, tried = _walk_lane(t, k, binds, pipelined)
+                tag = (t, k, binds, pipelined, steps)
+                # frames 1 .. t-1 each exactly once, in order; a one-frame sequence processes nothing
+                covered = [f for _, i, n in steps for f in range(i, i + n)]
+                assert covered == list(range(1, t)), tag
+                # no graph step (and no attempt to bind) before frame 2
+                assert all(i >= 2 for a, i, _ in steps if a in graph_acts) and all(i >= 2 for i in tried), tag
+                # the eager step for frame i memorizes exactly when i < t - 1
+                for a, i, n in steps:
+                    if a in (E.EAGER, E.EAGER_LAST):
+                        assert n == 1 and (a == E.EAGER) == (i < t - 1), tag
+                if not binds:
+                    assert all(a in (E.EAGER, E.EAGER_LAST) for a, _, _ in steps), tag
+                    continue
+                if k > 0:
+                    assert not any(a == E.GRAPH_FRAME for a, _, _ in steps), tag
+                    groups = [(a, i, n) for a, i, n in steps if a in graph_acts]
+                    for a, i, n in groups:
+                        # exactly k frames, never frame t - 1, replayed only while more than k frames remain
+                        assert n == k and i + n - 1 < t - 1 and t - i > k, tag
+                        # a following group is announced exactly when it will run
+                        assert (a == E.GROUP_AND_NEXT) == (t - (i + k) > k), tag
+                    if groups:
+                        # consecutive groups from one bind; the eager tail behind them is 1 .. k frames; no second bind
+                        assert [i for _, i, _ in groups] == list(range(groups[0][1], groups[0][1] + k * len(groups), k)), tag
+                        assert groups[-1][0] == E.LAST_GROUP and all(a == E.GROUP_AND_NEXT for a, _, _ in groups[:-1]), tag
+                        tail = [s for s in steps if s[1] >= groups[-1][1] + k]
+                        assert 1 <= len(tail) <= k and all(a in (E.EAGER, E.EAGER_LAST) for a, _, _ in tail), tag
+                        assert tried == [groups[0][1]], tag
+                    else:
+                        assert tried == [] and t - 2 <= k, tag        # (too short for a group behind the two eager frames)
+                else:
+                    assert not any(a in (E.GROUP_AND_NEXT, E.LAST_GROUP) for a, _, _ in steps), tag
+                    taken = [i for a, i, _ in steps if a == E.GRAPH_FRAME]
+                    # the plain FrameGraph never takes frame t - 1, the pipelined one may (and, once bound, does)
+                    assert (t - 1 in taken) == (pipelined and len(taken) > 0), tag
+                    assert taken == list(range(2, t if pipelined else t - 1)) or (t <= 3 and taken == []), tag
+                    assert len(tried) <= 1, tag
