@@ -587,6 +587,8 @@ extern "C" int swem_em_mstep_f32(void *stream, const float *A, int a_per_object,
   SWEM_REQUIRE(NK % 2 == 0 && L % 16 == 0 && R % 32 == 0, SWEM_E_SHAPE,
                "em_mstep: need NK even, L %% 16 == 0 and R %% 32 == 0 (got %d, %d, %d)", NK, L, R);
   SWEM_REQUIRE(!kp_out || !a_per_object, SWEM_E_SHAPE, "em_mstep: kp_out goes with the key rows (shared A)");
+  // (the pack's norm group has four slots, one per 32-row tile: more row tiles would write past a base's slots)
+  SWEM_REQUIRE(!kp_out || R == 64 || R == 128, SWEM_E_SHAPE, "em_mstep: packed keys need R = 64 or 128 rows (got %d)", R);
   if (a_per_object)  // value rows: A = v [N][P][R]
     return mstep_impl(stream, nullptr, A, z, nullptr, prev, zita_prev, nullptr, out, zita_out, nullptr, 0, 0, nullptr, 0, 0,
                       NK, 0, R, 0, R, P, L);

@@ -391,13 +391,16 @@ def test_heads_backward(lib):
     close(hm.grad.cpu(), masks.grad, 1e-6, 'd masks')
 
 
-@pytest.mark.parametrize('L,banks,topl,N', [(64, 1, 32, 2), (64, 2, 64, 2), (128, 2, 64, 2), (64, 2, 32, 5), (256, 2, 64, 2)])
-def test_match_backward(lib, L, banks, topl, N):
+@pytest.mark.parametrize('L,banks,topl,N,Cc', [(64, 1, 32, 2, 128), (64, 2, 64, 2, 128), (128, 2, 64, 2, 128), (64, 2, 32, 5, 128),
+                                               (256, 2, 64, 2, 128), (64, 2, 32, 2, 64), (256, 2, 64, 2, 64)],
+                         ids=['64-1-32-2', '64-2-64-2', '128-2-64-2', '64-2-32-5', '256-2-64-2', '64-2-32-2-c64', '256-2-64-2-c64'])
+def test_match_backward(lib, L, banks, topl, N, Cc):
     """get_affinity + perm_inv_feat: d qk (through the l2norm, the joint softmax and the top-l prefix features) and
-    d nu for both banks, against the oracle under autograd."""
+    d nu for both banks, against the oracle under autograd; key dimension 128 and 64 (the C = 64 instances of the affinity
+    kernel and the C-dependent GEMMs of swem_match_bwd_f32)."""
     from swem_amd import autograd as A
-    g = torch.Generator().manual_seed(12 + L + banks)
-    Cc, V, h, w = 128, 64, 6, 9
+    g = torch.Generator().manual_seed(12 + L + banks + (128 - Cc))
+    V, h, w = 64, 6, 9
     P = h * w
     xk, _ = H.structured_keys(P, Cc, 5, g)
     qk = leaf(xk.t().reshape(1, Cc, h, w).contiguous())
