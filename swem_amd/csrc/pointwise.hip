@@ -1286,11 +1286,14 @@ extern "C" int swem_cbam_f32_planes(void *stream, const float *x, const float *w
 }
 
 // backward of y = x + CBAM(x) (swem_cbam_f32): dx; the six parameter gradients are ACCUMULATED.
+// (the per-pixel sections are padded to whole float4s: the per-channel ones behind them are read 16 bytes at a time, and B * P is odd
+// on small maps)
+static inline size_t cbam_a4(size_t n) { return (n + 3) / 4 * 4; }
 extern "C" size_t swem_cbam_bwd_workspace(int B, int H, int W, int C) {
   const size_t P = (size_t)H * W;
   // part, comp, sg, da, dcomp | cscale, avg, max, dg, davg, dmax, amax | du, dxp
-  return ((size_t)B * CBAM_CHUNKS * 2 * C + (size_t)B * P * (2 + 1 + 1 + 2) + (size_t)B * C * 7 + 2 * (size_t)B * P * C) *
-         sizeof(float);
+  return ((size_t)B * CBAM_CHUNKS * 2 * C + 2 * cbam_a4((size_t)B * P * 2) + 2 * cbam_a4((size_t)B * P) + (size_t)B * C * 7 +
+          2 * (size_t)B * P * C) * sizeof(float);
 }
 extern "C" int swem_cbam_bwd_f32(void *stream, const float *x, const float *w1, const float *b1, const float *w2,
                                  const float *b2, const float *w7, const float *b7, const float *dy, float *dx,
@@ -1299,14 +1302,16 @@ extern "C" int swem_cbam_bwd_f32(void *stream, const float *x, const float *w1, 
   SWEM_REQUIRE(x && w1 && b1 && w2 && b2 && w7 && b7 && dy && dx && dw1 && db1 && dw2 && db2 && dw7 && db7, SWEM_E_ARG,
                "cbam_bwd: null pointer");
   SWEM_REQUIRE(C % 4 == 0 && C <= 4096 && hid > 0 && hid <= 256, SWEM_E_SHAPE, "cbam_bwd: unsupported C/hid");
+  // (cbam_bwd_mlp_kernel's LDS; refused before the first launch, so that a refused call has written nothing)
+  SWEM_REQUIRE((size_t)(9 * C + 4 * hid) * sizeof(float) <= 64 * 1024, SWEM_E_SHAPE, "cbam_bwd: C = %d, hid = %d need more than 64 KB of LDS", C, hid);
   SWEM_REQUIRE(ws && ws_bytes >= swem_cbam_bwd_workspace(B, H, W, C), SWEM_E_WORKSPACE, "cbam_bwd: workspace too small");
   const int P = H * W;
   float *part = static_cast<float *>(ws);
   float *comp = part + (size_t)B * CBAM_CHUNKS * 2 * C;
-  float *sg = comp + (size_t)B * P * 2;
-  float *da = sg + (size_t)B * P;
-  float *dcomp = da + (size_t)B * P;
-  float *cscale = dcomp + (size_t)B * P * 2;
+  float *sg = comp + cbam_a4((size_t)B * P * 2);
+  float *da = sg + cbam_a4((size_t)B * P);
+  float *dcomp = da + cbam_a4((size_t)B * P);
+  float *cscale = dcomp + cbam_a4((size_t)B * P * 2);
   float *avg = cscale + (size_t)B * C, *mx = avg + (size_t)B * C, *dg = mx + (size_t)B * C;
   float *davg = dg + (size_t)B * C, *dmx = davg + (size_t)B * C;
   int *amax = reinterpret_cast<int *>(dmx + (size_t)B * C);
@@ -1329,7 +1334,6 @@ extern "C" int swem_cbam_bwd_f32(void *stream, const float *x, const float *w1, 
   hipLaunchKernelGGL(cbam_bwd_pix2_kernel, grid1((long long)B * P * 64), dim3(256), 0, ST, x, dy, cscale, sg, comp,
                      dcomp, du, dxp, B, P, C);
   hipLaunchKernelGGL(cbam_bwd_dg_kernel, dim3(cdiv(C, 64), B), dim3(256), 0, ST, du, x, dg, P, C);
-  SWEM_REQUIRE((size_t)(9 * C + 4 * hid) * sizeof(float) <= 64 * 1024, SWEM_E_SHAPE, "cbam_bwd: C = %d, hid = %d need more than 64 KB of LDS", C, hid);
   hipLaunchKernelGGL(cbam_bwd_mlp_kernel, dim3(1), dim3(1024), (9 * C + 4 * hid) * sizeof(float), ST, avg, mx, cscale, dg, w1,
                      b1, w2, dw1, db1, dw2, db2, davg, dmx, B, C, hid);
   hipLaunchKernelGGL(cbam_bwd_pix3_kernel, grid1((long long)B * P * (C / 4)), dim3(256), 0, ST, dxp, davg, dmx, amax, dx,

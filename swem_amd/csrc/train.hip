@@ -1113,6 +1113,8 @@ extern "C" size_t swem_pred_head_bwd_workspace(int B, int H, int W, int C) {
 extern "C" int swem_pred_head_bwd_f32(void *stream, const float *x, const float *w, const float *dlogit, float *dx,
                                       float *dw, float *db, int B, int H, int W, int C, void *ws, size_t ws_bytes) {
   SWEM_REQUIRE(x && w && dlogit && dx && dw && db && C % 4 == 0, SWEM_E_ARG, "pred_head_bwd: bad argument");
+  // (pred_head_bwd_w_kernel's pixel lanes; refused before the first launch, so that a refused call has written nothing)
+  SWEM_REQUIRE(C > 0 && C / 4 <= 256 && 256 % (C / 4) == 0, SWEM_E_SHAPE, "pred_head_bwd: C / 4 must divide 256 (C = %d)", C);
   const size_t need = swem_pred_head_bwd_workspace(B, H, W, C);
   SWEM_REQUIRE(ws && ws_bytes >= need, SWEM_E_WORKSPACE, "pred_head_bwd: workspace %zu < %zu bytes", ws_bytes, need);
   const long long npix = (long long)B * H * W;
@@ -1120,7 +1122,6 @@ extern "C" int swem_pred_head_bwd_f32(void *stream, const float *x, const float 
   float *part = static_cast<float *>(ws);
   hipLaunchKernelGGL(pred_head_bwd_x_kernel, grid1t(npix * (C / 4)), dim3(256), 0, STT, x, w, dlogit, dx, B, H, W, C);
   SWEM_CHECK_LAUNCH("pred_head_bwd_x_kernel");
-  SWEM_REQUIRE(C / 4 <= 256 && 256 % (C / 4) == 0, SWEM_E_SHAPE, "pred_head_bwd: C / 4 must divide 256 (C = %d)", C);
   hipLaunchKernelGGL(pred_head_bwd_w_kernel, dim3(nchunk), dim3(256), (size_t)(256 / (C / 4)) * 9 * C * sizeof(float), STT, x, dlogit,
                      part, B, H, W, C);
   SWEM_CHECK_LAUNCH("pred_head_bwd_w_kernel");
