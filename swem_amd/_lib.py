@@ -1,4 +1,4 @@
-"""ctypes binding of libswem_hip.so (C ABI: include/swem_hip.h, swem_hip_train.h, swem_hip_metrics.h).
+"""ctypes binding of libswem_hip.so (C ABI: include/swem_hip.h, swem_hip_train.h, swem_hip_metrics.h, swem_hip_data.h).
 
 There is no CPU fallback: if the library is missing or a call fails this module raises.
 Build the library with ``python -m swem_amd.build`` (or ``__graft_entry__.build()``).
@@ -126,6 +126,9 @@ SIGNATURES = {
     # ---- include/swem_hip_metrics.h
     'swem_jf_workspace': (_sz, [_i, _i, _i, _i]),
     'swem_jf_counts_u8': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _sz]),
+    # ---- include/swem_hip_data.h
+    'swem_augment_workspace': (_sz, [_i, _i, _i, _i]),
+    'swem_augment_clips_u8': (_i, [_p] * 9 + [_i] * 7 + [_p, _sz]),
 }
 
 _lib = None

@@ -1448,6 +1448,32 @@ def flip_w(x):
     return resize_planes(x, tuple(x.shape[-2:]), 'flip')
 
 
+def augment_clips(src, lab, params, frames, masks, valid, label, found, ws, b0=0):
+    """swem_augment_clips_u8 (include/swem_hip_data.h): the clips of `src` (B,T,Hs,Ws,3) uint8 / `lab` (B,T,Hs,Ws) uint8 under the
+    packed device parameter block `params` into slots b0..b0+B-1 of the five outputs.  `ws`: a uint8 tensor of at least
+    swem_augment_workspace bytes (the caller's own: the warped labels and region codes stay readable in it)."""
+    for t, dt, name in ((src, torch.uint8, 'src'), (lab, torch.uint8, 'lab'), (frames, torch.float32, 'frames'),
+                        (masks, torch.float32, 'masks'), (valid, torch.float32, 'valid'), (label, torch.int64, 'label'),
+                        (found, torch.int32, 'found'), (ws, torch.uint8, 'ws')):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise _lib.SwemHipError('augment_clips: %s must be a contiguous %s device tensor (got %s %s contiguous=%s)'
+                                    % (name, dt, t.device, t.dtype, t.is_contiguous()))
+    B, T, Hs, Ws = lab.shape
+    Bo, To, C1, Ho, Wo = masks.shape
+    if tuple(src.shape) != (B, T, Hs, Ws, 3) or To != T or tuple(frames.shape) != (Bo, T, 3, Ho, Wo) or \
+            tuple(label.shape) != (Bo, T, Ho, Wo) or tuple(valid.shape) != (Bo, C1) or tuple(found.shape) != (Bo,):
+        raise _lib.SwemHipError('augment_clips: inconsistent shapes src %s lab %s frames %s masks %s valid %s label %s found %s'
+                                % tuple(tuple(t.shape) for t in (src, lab, frames, masks, valid, label, found)))
+    if not (0 <= b0 and b0 + B <= Bo):
+        raise _lib.SwemHipError('augment_clips: clips %d..%d do not fit a batch of %d' % (b0, b0 + B - 1, Bo))
+    words = B * T * 64 + B * 256
+    if not (params.is_cuda and params.is_contiguous() and params.element_size() == 4 and params.numel() >= words):
+        raise _lib.SwemHipError('augment_clips: params must be a contiguous device block of %d 32-bit words' % words)
+    _lib.call('swem_augment_clips_u8', _stream(), src.data_ptr(), lab.data_ptr(), params.data_ptr(), frames[b0:].data_ptr(),
+              masks[b0:].data_ptr(), valid[b0:].data_ptr(), label[b0:].data_ptr(), found[b0:].data_ptr(), B, T, Hs, Ws, Ho, Wo,
+              C1 - 1, ws.data_ptr(), ws.numel())
+
+
 def lincomb(a, alpha, b=None, beta=0.0):
     """alpha*a + beta*b on the device (TTA averaging)."""
     _chk(a)
