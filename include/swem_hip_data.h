@@ -30,7 +30,7 @@ extern "C" {
  *   18..33  TPS W_k of q_x, 34..49 of q_y, k = 4*row + column of the 4x4 anchor grid on [-1,1]^2
  *   50..52  clip-level factors (brightness, contrast, saturation), 53..55 frame-level factors
  *   56      int32: TPS on (non-zero) / off       57  int32: order of the clip-level ops     58  int32: grayscale on / off
- *   59      int32: order of the frame-level ops  60..63  zero
+ *   59      int32: order of the frame-level ops  60..63  zero (swem_augment_static_u8 reads them: below)
  * An order is three 2-bit op codes, first op in bits 0-1: 0 brightness, 1 contrast, 2 saturation, 3 no op.
  * Label order: the 256 labels in the order of the clip's random priority (the inverse of the priority permutation). */
 enum { SWEM_AUG_REGION_IMAGE = 0, SWEM_AUG_REGION_FILL = 1, SWEM_AUG_REGION_OUTSIDE_TPS = 2 };
@@ -53,6 +53,62 @@ size_t swem_augment_workspace(int B, int T, int Ho, int Wo);
 int swem_augment_clips_u8(void *stream, const unsigned char *src, const unsigned char *lab, const void *params, float *frames,
                           float *masks, float *valid, long long *label, int *found, int B, int T, int Hs, int Ws, int Ho,
                           int Wo, int N, void *ws, size_t ws_bytes);
+
+/* ---- Stage-0 training clips from static images (datasets/static_dataset.py) ------------------------------
+ *
+ * synthesis_frames (static_dataset.py:82-147): the objects of n_img images with masks are cut out at their bounding boxes and
+ * pasted, per frame at a drawn size and place and in a drawn order, onto image 0, whose own object is painted over with its
+ * mean colour.  The host draws the numbers; the device measures the boxes (integer min / max / add on words a launch has cleared:
+ * bitwise reproducible; a captured stage-0 call holds no memset node), evaluates random_resize /
+ * place_object in float64 (one thread per clip, frame and object) and gathers every output pixel once: nearest mask and cubic
+ * colour (A = -0.75) straight from the boxed source, no intermediate resize. */
+#define SWEM_SYNTH_MAX_IMAGES 7   /* N images per clip at the most (N + 1 <= SWEM_AUG_MAX_CHANNELS) */
+#define SWEM_SYNTH_CLIP_WORDS 32  /* 32-bit words of one clip's record */
+#define SWEM_SYNTH_FRAME_WORDS 64 /* 32-bit words of one frame's record */
+#define SWEM_SYNTH_STAT_WORDS 8   /* uint32 words of one image's statistics */
+#define SWEM_SYNTH_PLAN_WORDS 8   /* int32 words of one (frame, object) placement */
+/* Synth parameter block of a call over B clips of T frames (device memory, 4-byte aligned):
+ *   [B][SWEM_SYNTH_CLIP_WORDS] clip records, then [B][T][SWEM_SYNTH_FRAME_WORDS] frame records.
+ * Clip record (int32):
+ *    0        n_img, the images in use (1 <= n_img <= N; the device clamps it to that range)
+ *    2+2k     h_k,  3+2k  w_k: the real size of image k inside its slot, k < 7 (clamped to [1, Hmax] x [1, Wmax])
+ *   16+k      the label id of object k (the low 8 bits are used)                       the other words: zero
+ * Frame record:
+ *    0..6     int32 paste order: word p names the object pasted p-th (later ones cover earlier ones); an entry outside
+ *             [0, n_img) is skipped
+ *    8+4k..   fp32 area, aspect, ux, uy of object k: area the fraction of the box area (random_resize's scale), aspect its
+ *             width / height ratio, (ux, uy) in [0,1) the place (place_object's two randint draws)
+ * Image statistics in the workspace, [B][N][SWEM_SYNTH_STAT_WORDS] uint32 (foreground = mask != 0):
+ *    0  ~hmin   1  ~wmin   2  hmax + 1   3  wmax + 1  (all four built by integer max)   4  pixel count   5..7  sum of r, g, b
+ * Placement table, [B][T][N][SWEM_SYNTH_PLAN_WORDS] int32:  rh, rw, tx, ty, id, present, 0, 0  with (hc, wc) the box size,
+ *   rh = max(1, rint(sqrt(area hc wc / aspect))), rw = max(1, rint(sqrt(area hc wc aspect))),
+ *   tx = lo + min(hi - lo, floor(ux (hi - lo + 1))) - rw/2,  lo = rw/2, hi = max(w0 - rw/2, rw/2)  (integer halves; y alike),
+ *   present = 0 for k >= n_img and for an empty mask. */
+
+/* Workspace of a call: the statistics, then (256-byte aligned) the placement table.  0 for non-positive sizes. */
+size_t swem_synth_workspace(int B, int T, int N);
+
+/*   imgs     : [B][N][Hmax][Wmax][3] uint8 (HWC), each image at the top left of its slot; bytes outside its real size are never read
+ *   masks    : [B][N][Hmax][Wmax] uint8
+ *   params   : the synth block above
+ *   comp     : [B][T][Hmax][Wmax][3] uint8 composite frames, comp_lab : [B][T][Hmax][Wmax] uint8 labels -- both written at image
+ *              0's size (h_0 x w_0) only; with n_img == 1 they are image 0 and its mask bytes
+ *   1 <= N <= SWEM_SYNTH_MAX_IMAGES;  Hmax, Wmax <= 4096 (the uint32 colour sums hold 255 Hmax Wmax) */
+int swem_synth_frames_u8(void *stream, const unsigned char *imgs, const unsigned char *masks, const void *params,
+                         unsigned char *comp, unsigned char *comp_lab, int B, int T, int N, int Hmax, int Wmax, void *ws,
+                         size_t ws_bytes);
+
+/* The static chain (static_dataset.py:198-239) on composite frames: swem_augment_clips_u8 with words 60..63 of the frame record read:
+ *   60  int32 flags: bit 0: a pixel whose (sx, sy) lies outside [0, ws) x [0, hs) is FILL (the second fill test);
+ *                    bits 4-5: how many of the three clip-level ops run before the hue op
+ *   61, 62  int32: the clip's source height hs and width ws inside the slot (taps and labels clamp to them); a value outside
+ *           [1, Hs] / [1, Ws] means the call's Hs / Ws
+ *   63  fp32: the clip-level hue shift (torchvision's tensor form: RGB -> HSV, h = fmod(h + shift + 1, 1), back); 0: no hue op
+ * Hs, Ws are the slot size (the row and frame strides).  With words 60..63 zero the outputs are those of swem_augment_clips_u8,
+ * bit for bit. */
+int swem_augment_static_u8(void *stream, const unsigned char *src, const unsigned char *lab, const void *params, float *frames,
+                           float *masks, float *valid, long long *label, int *found, int B, int T, int Hs, int Ws, int Ho,
+                           int Wo, int N, void *ws, size_t ws_bytes);
 
 #ifdef __cplusplus
 }

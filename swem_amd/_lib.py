@@ -129,6 +129,9 @@ SIGNATURES = {
     # ---- include/swem_hip_data.h
     'swem_augment_workspace': (_sz, [_i, _i, _i, _i]),
     'swem_augment_clips_u8': (_i, [_p] * 9 + [_i] * 7 + [_p, _sz]),
+    'swem_augment_static_u8': (_i, [_p] * 9 + [_i] * 7 + [_p, _sz]),
+    'swem_synth_workspace': (_sz, [_i, _i, _i]),
+    'swem_synth_frames_u8': (_i, [_p] * 6 + [_i] * 5 + [_p, _sz]),
 }
 
 _lib = None

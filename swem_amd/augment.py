@@ -129,9 +129,12 @@ def draw_params(rng, T, src_hw, out_hw, is_bl=False):
 
 
 def frame_matrices(clip, frame):
-    """(M_aff, M_src) of one frame, float64 2x3 on (x, y, 1).  A frame may carry its own 'M_aff' instead of angle / shear."""
+    """(M_aff, M_src) of one frame, float64 2x3 on (x, y, 1).  A frame may carry its own 'M_aff' instead of angle / shear, and its
+    own 'M_src' instead of the clip's crop / flip (the static chain: `static_frame_matrices`)."""
     M_aff = np.asarray(frame['M_aff'], np.float64) if 'M_aff' in frame else \
         inverse_affine(frame.get('angle', 0.0), frame.get('shear', 0.0), clip['out_hw'])
+    if 'M_src' in frame:
+        return M_aff, np.asarray(frame['M_src'], np.float64)
     return M_aff, compose(M_aff, clip['crop'], clip['flip'], clip['out_hw'])
 
 
@@ -279,3 +282,236 @@ class ClipAugmenter:
         o = (2 * self._px(B) + 255) // 256 * 256
         words = self._buffers(B)[0][o:o + B * 32].view(torch.int32).view(B, 8)
         return ((words[:, :, None] >> torch.arange(32, device=words.device)) & 1).bool().view(B, 256)
+
+
+# ------------------------------------------------------------------------------------ stage 0: clips from static images
+# (datasets/static_dataset.py; csrc/synth.hip and the static form of csrc/augment.hip)
+SYNTH_CLIP_WORDS, SYNTH_FRAME_WORDS, SYNTH_STAT_WORDS, SYNTH_PLAN_WORDS, SYNTH_MAX_IMAGES = 32, 64, 8, 8, 7
+HUE = 3                                    # the fourth op of the clip-level jitter's drawn order
+FLAG_SRC_FILL = 1                          # word 60, bit 0: outside the source is FILL
+
+
+def static_scale(size0, out_hw):
+    """r of Resize(short side -> output) for image 0 of size (h0, w0): max(Ho/h0, Wo/w0)."""
+    return max(out_hw[0] / float(size0[0]), out_hw[1] / float(size0[1]))
+
+
+def draw_static_params(rng, T, sizes, out_hw):
+    """One static clip's parameters with the reference's distributions (static_dataset.py:43-79, 112-140, 198-239).  `sizes`: the
+    (h_k, w_k) of the n_img images, image 0 first.
+    synthesis: the ids, a shuffle of 1..n_img+1 of which the first n_img are used; per frame a paste order and per object fp32
+    (area U[0.16, 0.81), aspect log-uniform in [3/4, 4/3], ux, uy U[0, 1));
+    clip level: scale s1 U(0.8, 1.5) about the centre, flip p = 0.5; jitter brightness 0.9-1.1, contrast and saturation 0.95-1.05,
+    hue +-0.05 in a random order of the four; grayscale p = 0.05; the label priority permutation;
+    per frame: angle U(-20, 20), x-shear U(-10, 10), scale s2 U(0.9, 1.1); the crop offset; jitter 0.9-1.1 / 0.95-1.05 / 0.95-1.05
+    in random order; TPS (p = 1) with noise (U - 0.5) * 0.3 on the four inner anchors."""
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    n_img = len(sizes)
+    if not 1 <= n_img <= SYNTH_MAX_IMAGES:
+        raise ValueError('a static clip has 1..%d images, got %d' % (SYNTH_MAX_IMAGES, n_img))
+    Ho, Wo = out_hw
+    h0, w0 = sizes[0]
+    r = static_scale(sizes[0], out_hw)
+    p = {'sizes': sizes, 'out_hw': (int(Ho), int(Wo)), 'src_fill': True}
+    p['ids'] = [int(v) + 1 for v in rng.permutation(n_img + 1)[:n_img]]
+    p['s1'] = rng.uniform(0.8, 1.5)
+    p['flip'] = bool(rng.random() < 0.5)
+    four = [int(v) for v in rng.permutation(4)]
+    p['factors'] = (rng.uniform(0.9, 1.1), rng.uniform(0.95, 1.05), rng.uniform(0.95, 1.05))
+    p['hue'] = rng.uniform(-0.05, 0.05)
+    p['order'] = tuple(v for v in four if v != HUE)
+    p['hue_before'] = four.index(HUE)
+    p['gray'] = bool(rng.random() < 0.05)
+    p['prio'] = rng.permutation(256)
+    p['frames'] = []
+    for _ in range(T):
+        f = {'angle': rng.uniform(-20.0, 20.0), 'shear': rng.uniform(-10.0, 10.0), 's2': rng.uniform(0.9, 1.1)}
+        f['top'] = int(rng.integers(0, max(int(np.floor(r * h0)) - Ho, 0) + 1))
+        f['left'] = int(rng.integers(0, max(int(np.floor(r * w0)) - Wo, 0) + 1))
+        f['factors'] = (rng.uniform(0.9, 1.1), rng.uniform(0.95, 1.05), rng.uniform(0.95, 1.05))
+        f['order'] = tuple(int(v) for v in rng.permutation(3))
+        f['tps_on'] = True
+        Y = TPS_ANCHORS.copy()
+        Y[TPS_INNER] += (rng.random((4, 2)) - 0.5) * 0.3
+        f['tps_Y'] = Y
+        obj = np.empty((n_img, 4), np.float32)
+        obj[:, 0] = rng.uniform(0.16, 0.81, n_img)
+        obj[:, 1] = np.exp(rng.uniform(np.log(3.0 / 4.0), np.log(4.0 / 3.0), n_img))
+        obj[:, 2:] = rng.random((n_img, 2))
+        obj[:, 0] = np.minimum(obj[:, 0], np.nextafter(np.float32(0.81), np.float32(0)))     # (the cast may round up to the bound)
+        obj[:, 2:] = np.minimum(obj[:, 2:], np.nextafter(np.float32(1), np.float32(0)))
+        f['objects'] = obj
+        f['paste'] = [int(v) for v in rng.permutation(n_img)]
+        p['frames'].append(f)
+    return p
+
+
+def static_frame_matrices(clip, frame):
+    """(M_aff, M_src) of a static frame, float64 2x3 on (x, y, 1) = (u + 0.5, v + 0.5, 1): M_aff maps to
+    (px Wo / w0, py Ho / h0), so that the kernel's test against [0, Wo) x [0, Ho) is the test of (px, py) against image 0;
+    M_src is the whole map to the source coordinate (sx, sy)."""
+    Ho, Wo = clip['out_hw']
+    h0, w0 = clip['sizes'][0]
+    r = static_scale(clip['sizes'][0], clip['out_hw'])
+    c = np.array([w0 / 2.0, h0 / 2.0])
+    A2 = np.array([[1.0 / r, 0.0, frame.get('left', 0) / r], [0.0, 1.0 / r, frame.get('top', 0) / r], [0.0, 0.0, 1.0]])
+    inv = inverse_affine(frame.get('angle', 0.0), frame.get('shear', 0.0), (h0, w0))
+    s2 = float(frame.get('s2', 1.0))
+    A3 = np.eye(3)
+    A3[:2, :2] = inv[:, :2] / s2
+    A3[:2, 2] = c + (inv[:, 2] - c) / s2
+    P = A3 @ A2
+    F4 = np.array([[-1.0, 0.0, w0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]) if clip.get('flip', False) else np.eye(3)
+    s1 = float(clip.get('s1', 1.0))
+    A5 = np.eye(3)
+    A5[:2, :2] /= s1
+    A5[:2, 2] = c - c / s1
+    return (np.diag([Wo / float(w0), Ho / float(h0), 1.0]) @ P)[:2], (A5 @ F4 @ P)[:2]
+
+
+def pack_static_params(clips, max_images=None):
+    """(synth block, frame block) of a call for a list of clip dicts as `draw_static_params` returns them: two int32 arrays, of
+    B*32 + B*T*64 words (include/swem_hip_data.h, the synth record) and of B*T*64 + B*256 words (the frame record with words
+    60..63 set).  A missing key means the identity (no scale, no rotation, no hue, ...)."""
+    B, T = len(clips), len(clips[0]['frames'])
+    full = []
+    for clip in clips:
+        frames = []
+        for fr in clip['frames']:
+            M_aff, M_src = static_frame_matrices(clip, fr)
+            frames.append(dict(fr, M_aff=M_aff, M_src=M_src))
+        full.append(dict(clip, frames=frames))
+    block = pack_params(full)
+    fl = block.view(np.float32)
+    synth = np.zeros(B * SYNTH_CLIP_WORDS + B * T * SYNTH_FRAME_WORDS, np.int32)
+    sfl = synth.view(np.float32)
+    for b, clip in enumerate(clips):
+        sizes = clip['sizes']
+        n_img = len(sizes)
+        if not 1 <= n_img <= (SYNTH_MAX_IMAGES if max_images is None else max_images):
+            raise ValueError('clip %d has %d images' % (b, n_img))
+        before = int(clip.get('hue_before', 0))
+        if not 0 <= before <= 3:
+            raise ValueError('hue_before counts the clip-level ops in front of the hue op: 0..3')
+        o = b * SYNTH_CLIP_WORDS
+        synth[o] = n_img
+        ids = clip.get('ids', list(range(1, n_img + 1)))
+        for k, (h, w) in enumerate(sizes):
+            synth[o + 2 + 2 * k], synth[o + 3 + 2 * k] = int(h), int(w)
+            synth[o + 16 + k] = int(ids[k])
+        for t, fr in enumerate(clip['frames']):
+            o = (b * T + t) * FRAME_WORDS
+            block[o + 60] = (FLAG_SRC_FILL if clip.get('src_fill', True) else 0) | (before << 4)
+            block[o + 61], block[o + 62] = int(sizes[0][0]), int(sizes[0][1])
+            fl[o + 63] = clip.get('hue', 0.0)
+            o = B * SYNTH_CLIP_WORDS + (b * T + t) * SYNTH_FRAME_WORDS
+            paste = fr.get('paste', list(range(n_img)))
+            synth[o:o + len(paste)] = paste
+            synth[o + len(paste):o + SYNTH_MAX_IMAGES] = -1
+            if n_img > 1 or 'objects' in fr:
+                obj = np.asarray(fr['objects'], np.float32).reshape(n_img, 4)
+                sfl[o + 8:o + 8 + 4 * n_img] = obj.reshape(-1)
+    return synth, block
+
+
+class StaticClipSynthesizer(ClipAugmenter):
+    """callable(imgs_u8, masks_u8, params=None, out=None, b0=0) -> (frames, masks, valid_obj, label, found): stage-0 clips from
+    static images, `ClipAugmenter`'s call contract.
+
+    imgs_u8 (B,N,Hmax,Wmax,3) and masks_u8 (B,N,Hmax,Wmax): decoded uint8 images and masks on the device, each at the top left of its
+    slot (N = max_nobj, slot_hw = (Hmax, Wmax)); the real sizes travel in the parameters.  params: a list of B clip dicts
+    (`draw_static_params`), a pair of packed blocks (`pack_static_params`), or None = what the static buffers hold.
+    The composites (B,T,Hmax,Wmax,3) / (B,T,Hmax,Wmax) uint8 stay in this object's buffers (`composites`); statistics and the
+    placement table are readable through `stats` / `plan`.  Seven launches (the two clearing ones included; no memset node), no
+    host synchronisation, capturable."""
+
+    def __init__(self, out_hw, max_nobj, T, slot_hw, device=None):
+        super().__init__(out_hw, max_nobj, T, device)
+        self.slot_hw = (int(slot_hw[0]), int(slot_hw[1]))
+        if not 1 <= self.N <= SYNTH_MAX_IMAGES:
+            raise ValueError('StaticClipSynthesizer: 1 <= max_nobj <= %d, got %d' % (SYNTH_MAX_IMAGES, self.N))
+        self._synth = {}      # B -> (workspace, device block, pinned block, comp, comp_lab)
+
+    def _synth_buffers(self, B):
+        import torch
+        from . import _lib
+        st = self._synth.get(B)
+        if st is None:
+            nbytes = _lib.query('swem_synth_workspace', B, self.T, self.N)
+            if nbytes == 0:
+                raise _lib.SwemHipError('StaticClipSynthesizer: no workspace for B=%d T=%d N=%d' % (B, self.T, self.N))
+            words = B * SYNTH_CLIP_WORDS + B * self.T * SYNTH_FRAME_WORDS
+            Hm, Wm = self.slot_hw
+            st = (torch.zeros(nbytes, dtype=torch.uint8, device=self.device),
+                  torch.zeros(words, dtype=torch.int32, device=self.device), torch.zeros(words, dtype=torch.int32).pin_memory(),
+                  torch.zeros((B, self.T, Hm, Wm, 3), dtype=torch.uint8, device=self.device),
+                  torch.zeros((B, self.T, Hm, Wm), dtype=torch.uint8, device=self.device))
+            self._synth[B] = st
+        return st
+
+    def set_params(self, params, B=None):
+        """Copy a pair of packed blocks (or pack a list of clip dicts) into the static device buffers of its batch size."""
+        import torch
+        synth, block = params if isinstance(params, tuple) else pack_static_params(params, self.N)
+        if B is None:
+            B = block.size // (self.T * FRAME_WORDS + CLIP_WORDS)
+        _ws, sdev, spinned, _c, _l = self._synth_buffers(B)
+        if synth.dtype.itemsize != 4 or synth.size != spinned.numel():
+            raise ValueError('a synth block of B=%d, T=%d has %d 32-bit words, got %d' % (B, self.T, spinned.numel(), synth.size))
+        self._buffers(B)[3].synchronize()
+        spinned.numpy()[:] = synth.view(np.int32)
+        with torch.cuda.device(self.device):
+            sdev.copy_(spinned, non_blocking=True)
+        return super().set_params(block, B)          # (records the event behind both copies)
+
+    def __call__(self, imgs_u8, masks_u8, params=None, out=None, b0=0):
+        import torch
+        from . import ops
+        B = masks_u8.shape[0]
+        if tuple(masks_u8.shape[1:]) != (self.N,) + self.slot_hw:
+            raise ValueError('StaticClipSynthesizer was made for %d slots of %dx%d, got %s'
+                             % ((self.N,) + self.slot_hw + (tuple(masks_u8.shape),)))
+        if params is not None:
+            self.set_params(params, B)
+        ws, dev, _pinned, _done = self._buffers(B)
+        sws, sdev, _sp, comp, comp_lab = self._synth_buffers(B)
+        if out is None:
+            out = self.empty_out(B)
+        with torch.cuda.device(self.device):
+            ops.synth_frames(imgs_u8, masks_u8, sdev, comp, comp_lab, sws)
+            ops.augment_static(comp, comp_lab, dev, out[0], out[1], out[2], out[3], out[4], ws, b0)
+        return out
+
+    def warp(self, comp, comp_lab, params=None, out=None, b0=0):
+        """The second stage alone on given composites (B,T,Hmax,Wmax,3) / (B,T,Hmax,Wmax): the static chain of the parameters."""
+        import torch
+        from . import ops
+        B = comp_lab.shape[0]
+        if params is not None:
+            self.set_params(params, B)
+        ws, dev, _pinned, _done = self._buffers(B)
+        if out is None:
+            out = self.empty_out(B)
+        with torch.cuda.device(self.device):
+            ops.augment_static(comp, comp_lab, dev, out[0], out[1], out[2], out[3], out[4], ws, b0)
+        return out
+
+    # ---- what the last call of batch size B left behind (views / small copies, for checks)
+    def composites(self, B):
+        return self._synth_buffers(B)[3], self._synth_buffers(B)[4]
+
+    def stats(self, B):
+        """(B, N, 8) int64: hmin, wmin, hmax + 1, wmax + 1, count, sum r, sum g, sum b of every image's foreground (the box of
+        an empty mask is meaningless: count 0)."""
+        import torch
+        raw = self._synth_buffers(B)[0][:B * self.N * SYNTH_STAT_WORDS * 4].view(torch.int32).view(B, self.N, SYNTH_STAT_WORDS)
+        st = raw.to(torch.int64) & 0xffffffff
+        st[:, :, :2] = (~raw[:, :, :2]).to(torch.int64) & 0xffffffff
+        return st
+
+    def plan(self, B):
+        """(B, T, N, 6) int32: rh, rw, tx, ty, id, present of every (frame, object)."""
+        import torch
+        o = (B * self.N * SYNTH_STAT_WORDS * 4 + 255) // 256 * 256
+        n = B * self.T * self.N * SYNTH_PLAN_WORDS
+        return self._synth_buffers(B)[0][o:o + 4 * n].view(torch.int32).view(B, self.T, self.N, SYNTH_PLAN_WORDS)[..., :6]

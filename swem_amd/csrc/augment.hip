@@ -11,6 +11,11 @@
 #include "common.h"
 #include "../../include/swem_hip_data.h"
 
+// Both forms of the two kernels (the clips' and the static chain's) must give the same bits where their parameters agree.  hipcc's
+// default lets the back end fuse a multiply and an add wherever it finds them, which it decided differently in the two
+// instantiations; `on` fuses exactly the a * b + c of one expression, so the arithmetic is what the source lines say.
+#pragma clang fp contract(on)
+
 namespace {
 
 #define AUG_TW 32   // tile width  (a wave covers two rows of 32 pixels)
@@ -57,6 +62,25 @@ __device__ __forceinline__ void jitter(float &r, float &g, float &b, int code, c
   }
 }
 
+// torchvision's adjust_hue on floats in [0,1] (_rgb2hsv / _hsv2rgb, the vector form of colorsys): h <- fmod(h + shift + 1, 1)
+__device__ __forceinline__ void hue_shift(float &r, float &g, float &b, float shift) {
+  const float maxc = fmaxf(r, fmaxf(g, b)), minc = fminf(r, fminf(g, b));
+  const bool eqc = maxc == minc;
+  const float cr = maxc - minc;
+  const float s = cr / (eqc ? 1.f : maxc), crd = eqc ? 1.f : cr;
+  const float rc = (maxc - r) / crd, gc = (maxc - g) / crd, bc = (maxc - b) / crd;
+  float h = maxc == r ? bc - gc : (maxc == g ? 2.f + rc - bc : 4.f + gc - rc);
+  h = fmodf(h / 6.f + 1.f, 1.f);
+  h = fmodf(h + shift + 1.f, 1.f);
+  const float h6 = h * 6.f, fi = floorf(h6), f = h6 - fi;
+  const int i = ((int)fi) % 6;
+  const float v = maxc;
+  const float p = clamp01(v * (1.f - s)), q = clamp01(v * (1.f - s * f)), t = clamp01(v * (1.f - s * (1.f - f)));
+  r = i == 0 || i == 5 ? v : (i == 1 ? q : (i == 4 ? t : p));
+  g = i == 1 || i == 2 ? v : (i == 3 ? q : (i == 0 ? t : p));
+  b = i == 3 || i == 4 ? v : (i == 5 ? q : (i == 2 ? t : p));
+}
+
 // fixed-order sum over the block: lanes by shuffles, the four waves in order.  Every thread returns the same value.
 __device__ __forceinline__ float block_sum(float v, float *red) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
@@ -65,6 +89,13 @@ __device__ __forceinline__ float block_sum(float v, float *red) {
   return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+__global__ __launch_bounds__(256) void aug_clear_kernel(unsigned *__restrict__ words, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) words[i] = 0u;
+}
+
+// STATIC: the static chain's form (swem_augment_static_u8), which reads words 60..63 of the frame record
+template <bool STATIC>
 __global__ __launch_bounds__(256) void aug_warp_kernel(const unsigned char *__restrict__ src, const unsigned char *__restrict__ lab,
                                                        const float *__restrict__ params, float *__restrict__ frames,
                                                        unsigned char *__restrict__ wlab, unsigned char *__restrict__ wreg,
@@ -78,6 +109,14 @@ __global__ __launch_bounds__(256) void aug_warp_kernel(const unsigned char *__re
   const int *PI = reinterpret_cast<const int *>(P);
   if (threadIdx.x < 8) pres[threadIdx.x] = 0u;
   __syncthreads();
+  // the source inside its slot: Hs, Ws stay the strides
+  int hs = Hs, ws = Ws;
+  bool src_fill = false;
+  if constexpr (STATIC) {
+    if (PI[61] >= 1 && PI[61] <= Hs) hs = PI[61];
+    if (PI[62] >= 1 && PI[62] <= Ws) ws = PI[62];
+    src_fill = (PI[60] & 1) != 0;
+  }
 
   const int i = (tile % tiles_x) * AUG_TW + (threadIdx.x & (AUG_TW - 1));
   const int j = (tile / tiles_x) * AUG_TH + (threadIdx.x / AUG_TW);
@@ -105,8 +144,9 @@ __global__ __launch_bounds__(256) void aug_warp_kernel(const unsigned char *__re
     // 2. affine, 3. crop and flip: two affine forms of the centred coordinate
     const float xc = u + 0.5f - 0.5f * (float)Wo, yc = v + 0.5f - 0.5f * (float)Ho;
     const float xa = P[0] * xc + P[1] * yc + P[2], ya = P[3] * xc + P[4] * yc + P[5];
-    const bool fill = xa < 0.f || xa >= (float)Wo || ya < 0.f || ya >= (float)Ho;
+    bool fill = xa < 0.f || xa >= (float)Wo || ya < 0.f || ya >= (float)Ho;
     const float sx = P[6] * xc + P[7] * yc + P[8], sy = P[9] * xc + P[10] * yc + P[11];
+    if constexpr (STATIC) fill = fill || (src_fill && (sx < 0.f || sx >= (float)ws || sy < 0.f || sy >= (float)hs));
     // 4. sample
     float r = 0.f, g = 0.f, bl = 0.f;
     int l = 0, region = SWEM_AUG_REGION_IMAGE;
@@ -119,7 +159,7 @@ __global__ __launch_bounds__(256) void aug_warp_kernel(const unsigned char *__re
       bl = 104.f / 255.f;
     } else {
       const size_t frame_px = bt * Hs * Ws;
-      const int lx = min(max((int)floorf(sx), 0), Ws - 1), ly = min(max((int)floorf(sy), 0), Hs - 1);
+      const int lx = min(max((int)floorf(sx), 0), ws - 1), ly = min(max((int)floorf(sy), 0), hs - 1);
       l = lab[frame_px + (size_t)ly * Ws + lx];
       const unsigned char *S = src + frame_px * 3;
       const float bx = sx - 0.5f, by = sy - 0.5f;
@@ -130,10 +170,10 @@ __global__ __launch_bounds__(256) void aug_warp_kernel(const unsigned char *__re
       const float wy[4] = {aug_cubic2(ty + 1.f), aug_cubic1(ty), aug_cubic1(1.f - ty), aug_cubic2(2.f - ty)};
       int xo[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) xo[q] = 3 * min(max(ix - 1 + q, 0), Ws - 1);
+      for (int q = 0; q < 4; ++q) xo[q] = 3 * min(max(ix - 1 + q, 0), ws - 1);
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
-        const unsigned char *row = S + (size_t)min(max(iy - 1 + a, 0), Hs - 1) * Ws * 3;
+        const unsigned char *row = S + (size_t)min(max(iy - 1 + a, 0), hs - 1) * Ws * 3;
         float rr = 0.f, rg = 0.f, rb = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -165,6 +205,7 @@ __global__ __launch_bounds__(256) void aug_warp_kernel(const unsigned char *__re
   if (t == 0 && threadIdx.x < 8 && pres[threadIdx.x]) atomicOr(presence + (size_t)b * 8 + threadIdx.x, pres[threadIdx.x]);
 }
 
+template <bool STATIC>
 __global__ __launch_bounds__(256) void aug_finish_kernel(const float *__restrict__ params, float *__restrict__ frames,
                                                          float *__restrict__ masks, float *__restrict__ valid,
                                                          long long *__restrict__ label, int *__restrict__ found,
@@ -223,7 +264,16 @@ __global__ __launch_bounds__(256) void aug_finish_kernel(const float *__restrict
   float *F = frames + bt * 3 * plane + pix;
   float r = F[0], g = F[plane], bl = F[2 * plane];
   if (region == SWEM_AUG_REGION_IMAGE) {   // (the fill enters after the clip-level ops)
-    jitter(r, g, bl, PI[57], P + 50, mean);
+    bool hue = false;
+    if constexpr (STATIC) hue = P[63] != 0.f;
+    if (hue) {   // the clip-level jitter's four ops: `before` of the three, the hue op, the rest
+      const int before = (PI[60] >> 4) & 3;
+      jitter(r, g, bl, PI[57] | (0x3f << (2 * before)), P + 50, mean);
+      hue_shift(r, g, bl, P[63]);
+      jitter(r, g, bl, PI[57] | ((1 << (2 * before)) - 1), P + 50, mean);
+    } else {
+      jitter(r, g, bl, PI[57], P + 50, mean);
+    }
     if (PI[58]) r = g = bl = gray_of(r, g, bl);
   }
   jitter(r, g, bl, PI[59], P + 53, mean);
@@ -241,39 +291,62 @@ extern "C" size_t swem_augment_workspace(int B, int T, int Ho, int Wo) {
   return aug_layout(B, T, Ho, Wo).total;
 }
 
-extern "C" int swem_augment_clips_u8(void *stream, const unsigned char *src, const unsigned char *lab, const void *params,
-                                     float *frames, float *masks, float *valid, long long *label, int *found, int B, int T,
-                                     int Hs, int Ws, int Ho, int Wo, int N, void *ws, size_t ws_bytes) {
-  SWEM_REQUIRE(src && lab && params && frames && masks && valid && label && found && ws, SWEM_E_ARG,
-               "augment_clips: null pointer");
+namespace {
+template <bool STATIC>
+int augment_launch(const char *who, void *stream, const unsigned char *src, const unsigned char *lab, const void *params,
+                   float *frames, float *masks, float *valid, long long *label, int *found, int B, int T, int Hs, int Ws, int Ho,
+                   int Wo, int N, void *ws, size_t ws_bytes) {
+  SWEM_REQUIRE(src && lab && params && frames && masks && valid && label && found && ws, SWEM_E_ARG, "%s: null pointer", who);
   SWEM_REQUIRE(((uintptr_t)params % 4) == 0 && ((uintptr_t)ws % 4) == 0 && ((uintptr_t)label % 8) == 0, SWEM_E_ARG,
-               "augment_clips: params and ws must be 4-byte aligned, label 8-byte aligned");
-  SWEM_REQUIRE(B > 0 && T > 0 && Hs > 0 && Ws > 0, SWEM_E_SHAPE, "augment_clips: need B, T, Hs, Ws > 0, got B=%d T=%d Hs=%d Ws=%d",
-               B, T, Hs, Ws);
-  SWEM_REQUIRE(Ho >= 2 && Wo >= 2, SWEM_E_SHAPE, "augment_clips: need an output of at least 2x2 (the TPS grid divides by Ho-1, "
-               "Wo-1), got %dx%d", Ho, Wo);
-  SWEM_REQUIRE(N >= 1 && N + 1 <= SWEM_AUG_MAX_CHANNELS, SWEM_E_SHAPE,
-               "augment_clips: need 1 <= N and N + 1 <= %d mask channels, got N=%d", SWEM_AUG_MAX_CHANNELS, N);
-  SWEM_REQUIRE(B <= 65535 && T <= 65535, SWEM_E_SHAPE, "augment_clips: B=%d, T=%d exceed one launch (65535 each)", B, T);
+               "%s: params and ws must be 4-byte aligned, label 8-byte aligned", who);
+  SWEM_REQUIRE(B > 0 && T > 0 && Hs > 0 && Ws > 0, SWEM_E_SHAPE, "%s: need B, T, Hs, Ws > 0, got B=%d T=%d Hs=%d Ws=%d", who, B, T,
+               Hs, Ws);
+  SWEM_REQUIRE(Ho >= 2 && Wo >= 2, SWEM_E_SHAPE, "%s: need an output of at least 2x2 (the TPS grid divides by Ho-1, Wo-1), got %dx%d",
+               who, Ho, Wo);
+  SWEM_REQUIRE(N >= 1 && N + 1 <= SWEM_AUG_MAX_CHANNELS, SWEM_E_SHAPE, "%s: need 1 <= N and N + 1 <= %d mask channels, got N=%d", who,
+               SWEM_AUG_MAX_CHANNELS, N);
+  SWEM_REQUIRE(B <= 65535 && T <= 65535, SWEM_E_SHAPE, "%s: B=%d, T=%d exceed one launch (65535 each)", who, B, T);
   SWEM_REQUIRE((long long)Hs * Ws <= 0x7fffffffLL / 3 && (long long)Ho * Wo <= 0x7fffffffLL, SWEM_E_SHAPE,
-               "augment_clips: a frame of %dx%d -> %dx%d exceeds 32-bit pixel offsets", Hs, Ws, Ho, Wo);
+               "%s: a frame of %dx%d -> %dx%d exceeds 32-bit pixel offsets", who, Hs, Ws, Ho, Wo);
   const AugLayout L = aug_layout(B, T, Ho, Wo);
-  SWEM_REQUIRE(ws_bytes >= L.total, SWEM_E_WORKSPACE, "augment_clips: workspace %zu < %zu bytes", ws_bytes, L.total);
+  SWEM_REQUIRE(ws_bytes >= L.total, SWEM_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, L.total);
   unsigned char *w = static_cast<unsigned char *>(ws);
   unsigned *presence = reinterpret_cast<unsigned *>(w + L.presence);
   float *partial = reinterpret_cast<float *>(w + L.partial);
-  hipError_t e = hipMemsetAsync(presence, 0, (size_t)B * 8 * sizeof(unsigned), ST);
-  if (e != hipSuccess) {
-    swem_set_error("augment_clips: hipMemsetAsync: %s", hipGetErrorString(e));
-    return SWEM_E_HIP;
+  if constexpr (STATIC) {
+    // a launch, not a memset node: replayed back to back, a captured call's memset node was seen to leave a stale pattern in
+    // the presence set; the clips' entry keeps its memset node, as it always had
+    hipLaunchKernelGGL(aug_clear_kernel, dim3((unsigned)cdiv((long long)B * 8, 256)), dim3(256), 0, ST, presence, B * 8);
+    SWEM_CHECK_LAUNCH("aug_clear");
+  } else {
+    hipError_t e = hipMemsetAsync(presence, 0, (size_t)B * 8 * sizeof(unsigned), ST);
+    if (e != hipSuccess) {
+      swem_set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
+      return SWEM_E_HIP;
+    }
   }
   const dim3 grid((unsigned)L.tiles, (unsigned)T, (unsigned)B);
   const float *par = static_cast<const float *>(params);
-  hipLaunchKernelGGL(aug_warp_kernel, grid, dim3(256), 0, ST, src, lab, par, frames, w + L.wlab, w + L.wreg, partial, presence,
-                     T, Hs, Ws, Ho, Wo, L.tiles_x, L.tiles);
+  hipLaunchKernelGGL(aug_warp_kernel<STATIC>, grid, dim3(256), 0, ST, src, lab, par, frames, w + L.wlab, w + L.wreg, partial,
+                     presence, T, Hs, Ws, Ho, Wo, L.tiles_x, L.tiles);
   SWEM_CHECK_LAUNCH("aug_warp");
-  hipLaunchKernelGGL(aug_finish_kernel, grid, dim3(256), 0, ST, par, frames, masks, valid, label, found, w + L.wlab, w + L.wreg,
-                     partial, presence, B, T, Ho, Wo, N, L.tiles_x, L.tiles);
+  hipLaunchKernelGGL(aug_finish_kernel<STATIC>, grid, dim3(256), 0, ST, par, frames, masks, valid, label, found, w + L.wlab,
+                     w + L.wreg, partial, presence, B, T, Ho, Wo, N, L.tiles_x, L.tiles);
   SWEM_CHECK_LAUNCH("aug_finish");
   return SWEM_OK;
+}
+}  // namespace
+
+extern "C" int swem_augment_clips_u8(void *stream, const unsigned char *src, const unsigned char *lab, const void *params,
+                                     float *frames, float *masks, float *valid, long long *label, int *found, int B, int T,
+                                     int Hs, int Ws, int Ho, int Wo, int N, void *ws, size_t ws_bytes) {
+  return augment_launch<false>("augment_clips", stream, src, lab, params, frames, masks, valid, label, found, B, T, Hs, Ws, Ho, Wo,
+                               N, ws, ws_bytes);
+}
+
+extern "C" int swem_augment_static_u8(void *stream, const unsigned char *src, const unsigned char *lab, const void *params,
+                                      float *frames, float *masks, float *valid, long long *label, int *found, int B, int T,
+                                      int Hs, int Ws, int Ho, int Wo, int N, void *ws, size_t ws_bytes) {
+  return augment_launch<true>("augment_static", stream, src, lab, params, frames, masks, valid, label, found, B, T, Hs, Ws, Ho, Wo,
+                              N, ws, ws_bytes);
 }

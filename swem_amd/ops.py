@@ -1448,7 +1448,7 @@ def flip_w(x):
     return resize_planes(x, tuple(x.shape[-2:]), 'flip')
 
 
-def augment_clips(src, lab, params, frames, masks, valid, label, found, ws, b0=0):
+def augment_clips(src, lab, params, frames, masks, valid, label, found, ws, b0=0, entry='swem_augment_clips_u8'):
     """swem_augment_clips_u8 (include/swem_hip_data.h): the clips of `src` (B,T,Hs,Ws,3) uint8 / `lab` (B,T,Hs,Ws) uint8 under the
     packed device parameter block `params` into slots b0..b0+B-1 of the five outputs.  `ws`: a uint8 tensor of at least
     swem_augment_workspace bytes (the caller's own: the warped labels and region codes stay readable in it)."""
@@ -1469,9 +1469,37 @@ def augment_clips(src, lab, params, frames, masks, valid, label, found, ws, b0=0
     words = B * T * 64 + B * 256
     if not (params.is_cuda and params.is_contiguous() and params.element_size() == 4 and params.numel() >= words):
         raise _lib.SwemHipError('augment_clips: params must be a contiguous device block of %d 32-bit words' % words)
-    _lib.call('swem_augment_clips_u8', _stream(), src.data_ptr(), lab.data_ptr(), params.data_ptr(), frames[b0:].data_ptr(),
+    _lib.call(entry, _stream(), src.data_ptr(), lab.data_ptr(), params.data_ptr(), frames[b0:].data_ptr(),
               masks[b0:].data_ptr(), valid[b0:].data_ptr(), label[b0:].data_ptr(), found[b0:].data_ptr(), B, T, Hs, Ws, Ho, Wo,
               C1 - 1, ws.data_ptr(), ws.numel())
+
+
+def augment_static(src, lab, params, frames, masks, valid, label, found, ws, b0=0):
+    """swem_augment_static_u8: `augment_clips` in the static chain's form (words 60..63 of the frame record are read; the last two
+    dims of `lab` are the slot size)."""
+    augment_clips(src, lab, params, frames, masks, valid, label, found, ws, b0, entry='swem_augment_static_u8')
+
+
+def synth_frames(imgs, masks, params, comp, comp_lab, ws):
+    """swem_synth_frames_u8 (include/swem_hip_data.h): `imgs` (B,N,Hmax,Wmax,3) / `masks` (B,N,Hmax,Wmax) uint8 slots under the
+    packed device synth block `params` into the composites `comp` (B,T,Hmax,Wmax,3) and their labels `comp_lab` (B,T,Hmax,Wmax).
+    `ws`: a uint8 tensor of at least swem_synth_workspace bytes (statistics and placement table stay readable in it)."""
+    for t, name in ((imgs, 'imgs'), (masks, 'masks'), (comp, 'comp'), (comp_lab, 'comp_lab'), (ws, 'ws')):
+        if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise _lib.SwemHipError('synth_frames: %s must be a contiguous uint8 device tensor (got %s %s contiguous=%s)'
+                                    % (name, t.device, t.dtype, t.is_contiguous()))
+    if masks.dim() != 4 or comp_lab.dim() != 4:
+        raise _lib.SwemHipError('synth_frames: masks and comp_lab are 4-d, got %s %s' % (tuple(masks.shape), tuple(comp_lab.shape)))
+    B, N, Hm, Wm = masks.shape
+    T = comp_lab.shape[1]
+    if tuple(imgs.shape) != (B, N, Hm, Wm, 3) or tuple(comp_lab.shape) != (B, T, Hm, Wm) or tuple(comp.shape) != (B, T, Hm, Wm, 3):
+        raise _lib.SwemHipError('synth_frames: inconsistent shapes imgs %s masks %s comp %s comp_lab %s'
+                                % tuple(tuple(t.shape) for t in (imgs, masks, comp, comp_lab)))
+    words = B * 32 + B * T * 64
+    if not (params.is_cuda and params.is_contiguous() and params.element_size() == 4 and params.numel() >= words):
+        raise _lib.SwemHipError('synth_frames: params must be a contiguous device block of %d 32-bit words' % words)
+    _lib.call('swem_synth_frames_u8', _stream(), imgs.data_ptr(), masks.data_ptr(), params.data_ptr(), comp.data_ptr(),
+              comp_lab.data_ptr(), B, T, N, Hm, Wm, ws.data_ptr(), ws.numel())
 
 
 def lincomb(a, alpha, b=None, beta=0.0):
