@@ -15,12 +15,15 @@ number of GPUs only if asked (solver.py:31-34, ``num_gpu``), so does ``SWEMTrain
 How the batch is run: clips are independent (frozen BatchNorm, per-clip memory), so every clip is its own forward /
 per-clip loss with weight 1/B / backward.  Up to ``lanes`` clips are in flight at once, each on its own stream with its
 own flat gradient buffer (the in-kernel accumulation is a plain read-modify-write); the lanes' buffers are summed into
-the optimizer's.  That equals the reference's batched step (``total = mean_b``).  Mixed precision (config.AMP): the
-convolutions' forward and data gradient take bf16 operands (one MFMA product, fp32 accumulate); everything else is fp32.
+the optimizer's.  That equals the reference's batched step (``total = mean_b``).  The order of a step's parts and the edges
+between the streams are the list ``step_schedule`` returns; eager steps, capture and replay all walk it.  Mixed precision
+(config.AMP): the convolutions' forward and data gradient take bf16 operands (one MFMA product, fp32 accumulate); everything
+else is fp32.
 """
 import contextlib
 import math
 import os
+import warnings
 
 import torch
 
@@ -208,6 +211,28 @@ def random_init_host(B, N, Cc, Lb):
 #   1/16-scale layers: 36-72 tiles on 256 CUs) loses the 1.95x overlap four concurrent lanes get: the lanes keep the default.
 DEFAULT_LANES = 4
 
+# The training step as data: what `SWEMTrainer._step` walks, eagerly, capturing or replaying.
+MAIN, LANE, FORK, JOIN, HOST = 'main', 'lane', 'fork', 'join', 'host'     # the kinds of operation of `step_schedule`
+EAGER, CAPTURE, REPLAY = 'eager', 'capture', 'replay'                     # the ways `SWEMTrainer._step` walks it
+
+
+def step_schedule(n_lanes):
+    """One training step on `n_lanes` lanes as a list of (kind, part, lane): (MAIN, part, None) runs a part on the main stream,
+    (LANE, part, l) on lane l's stream, (FORK, None, l) lets lane l's stream wait for the main stream, (JOIN, None, l) the main
+    stream for lane l's, (HOST, part, None) is a call on the host that is never captured.  The parts (SWEMTrainer): `pre` = `_pre`,
+    `packs` = `_packs` (every lane reads every pack: all lanes are joined before any starts phase A), `a` = `_lane`, `rest` =
+    `_post_rest` (+ the captured all-reduce with reduce_in_graph), `reduce_rest` = `_reduce_rest`, `b` = `_lane_trunk`, `post` =
+    `_post`.  There is NO fork in front of `b`: phase B is ordered behind the same lane's phase A by stream order alone, not
+    behind `rest` or the all-reduce launched on the main stream -- a fork there would serialise the trunk's backward behind the
+    gradient sum and the collective it is meant to hide."""
+    lanes = range(n_lanes)
+    fork, join = [(FORK, None, l) for l in lanes], [(JOIN, None, l) for l in lanes]
+
+    def on_lanes(part):
+        return [(LANE, part, l) for l in lanes]
+    return ([(MAIN, 'pre', None)] + fork + on_lanes('packs') + join + fork + on_lanes('a') + join
+            + [(MAIN, 'rest', None), (HOST, 'reduce_rest', None)] + on_lanes('b') + join + [(MAIN, 'post', None)])
+
 
 class SWEMTrainer:
     """swem_trainer.py:19-108 without the dataset / logging plumbing: model, criterion, optimizer, scheduler, one_step."""
@@ -277,6 +302,14 @@ class SWEMTrainer:
         self.wgrad_stream = bool(int(os.environ.get('SWEM_TRAIN_WGRAD_STREAM', 1 if self.lanes == 1 else 0))) if wgrad_stream is None \
             else bool(wgrad_stream)
         self._lane_state = None
+        # the step's static input buffers (`_static`) and what was captured on them: `_graph` None = not captured (set it to
+        # None and the next step captures again), else {(part, lane): HIP graph} with the captured results in `_graph_out`
+        self.buf = self._static_key = self._gout_for = None
+        self._graph = self._graph_out = None
+        self._eager_steps = self._steps_seen = 0
+        self.fault_check_every = 20                  # the host looks at the fault flags every so many steps (one_step)
+        self._kappa_ring = {}
+        self._results, self._lane_trunks = [], []
         self._foreign_fault = 0
         ops.fault_word(dev)
         ops.register_fault_owner(self)
@@ -319,7 +352,7 @@ class SWEMTrainer:
     def _static(self, frames, init_mask, valid_obj, label):
         """Device buffers with fixed addresses for the step's inputs (a captured HIP graph replays on them)."""
         key = (tuple(frames.shape), tuple(init_mask.shape), valid_obj is not None)
-        if getattr(self, '_static_key', None) != key:
+        if self._static_key != key:
             core = self.model.swem_core
             B, N = frames.shape[0], init_mask.shape[1] - 1
             Ck = self.model.key_proj.key_proj.weight.shape[0]
@@ -440,41 +473,64 @@ class SWEMTrainer:
         bf['sums'][:3].copy_(tot)
         return torch.cat(self._results, dim=0)
 
-    def _clips(self, cur_iter):
-        """zero_grad + forward / loss / backward of every clip on the static buffers; returns (results, p).
+    def _step(self, mode, cur_iter=None):
+        """Walk `step_schedule` once.  EAGER: every part runs on its stream (zero_grad + forward / loss / backward of every clip
+        on the static buffers); returns (results, p), p from the last lane's phase A.  CAPTURE: every part becomes a HIP graph
+        of its own, kept in `self._graph[part, lane]` (the captured results in `self._graph_out`).  REPLAY: those graphs.
         Data parallel: the all-reduce of the non-trunk gradient (6/7 of the parameters) is started as soon as every lane has
-        finished phase A and runs while the lanes back-propagate through the key-encoder trunk."""
+        finished phase A and runs while the lanes back-propagate through the key-encoder trunk.
+
+        CAPTURE: one HIP graph per part -- `pre`, `rest` and `post` on the main stream, one graph per lane and part on the
+        lane's own (probed) stream.  A single graph with forked branches leaves the placement of the branches to the runtime,
+        and two lanes on one hardware queue serialise (measured: 40 to 56 clips/s from run to run); separate graphs replay on
+        the streams that `evaluator.overlapping_streams` found to overlap."""
         ls = self._lanes(self.buf['init_mask'].shape[0])
         main = torch.cuda.current_stream()
-        self._pre()
-        p = 1.0
-        for st in ls['streams']:
-            if st is not None:
-                st.wait_stream(main)                                   # fork: the re-pack, a share per lane
-        for l, st in enumerate(ls['streams']):
-            with torch.cuda.stream(st if st is not None else main):
-                self._packs(l)
-        for st in ls['streams']:
-            if st is not None:
-                main.wait_stream(st)                                   # every pack is there ...
-        for st in ls['streams']:
-            if st is not None:
-                st.wait_stream(main)                                   # ... before any lane reads one
-        for l, st in enumerate(ls['streams']):
-            with torch.cuda.stream(st if st is not None else main):
-                p = self._lane(l, cur_iter)
-        for st in ls['streams']:
-            if st is not None:
-                main.wait_stream(st)                                   # phase A of every lane
-        self._post_rest()
-        self._reduce_rest()
-        for l, st in enumerate(ls['streams']):
-            with torch.cuda.stream(st if st is not None else main):
-                self._lane_trunk(l)
-        for st in ls['streams']:
-            if st is not None:
-                main.wait_stream(st)                                   # join
-        return self._post(), p
+        capture = mode == CAPTURE
+        graphs = {} if capture else self._graph
+
+        def rest(_):
+            self._post_rest()
+            if capture and self.reduce_in_graph:
+                self._reduce_rest(captured=True)
+        # (every part is called with its lane; the main stream's parts have none)
+        parts = {'pre': lambda _: self._pre(), 'packs': self._packs, 'a': lambda l: self._lane(l, cur_iter), 'rest': rest,
+                 'reduce_rest': lambda _: self._reduce_rest(), 'b': self._lane_trunk, 'post': lambda _: self._post()}
+        out = {}
+        if capture:
+            torch.cuda.synchronize()
+            # (scratch buffers of the captured launches are allocated inside the captures, ops.workspace: the eager warm-up
+            # steps left cached workspaces on these very streams, and a graph must not point into a cache entry that a later,
+            # larger eager request -- e.g. 480p validation between steps -- replaces)
+            cap = ops.graph_capture_kwargs()   # ("thread_local" while a process group's watchdog thread is alive: ops.py)
+        with contextlib.nullcontext() if mode == REPLAY else self._math():
+            for kind, part, l in step_schedule(len(ls['streams'])):
+                # a lane whose stream is None is the single lane on the caller's stream: nothing to fork or join, captured
+                # without `stream=`, run and replayed on the current stream (as the main parts are: they carry no lane)
+                st = None if l is None else ls['streams'][l]
+                if kind in (FORK, JOIN):
+                    if st is not None:
+                        waits, on = (st, main) if kind == FORK else (main, st)
+                        waits.wait_stream(on)
+                elif kind == HOST:
+                    if not capture:
+                        parts[part](l)                     # (the all-reduce: in flight while the lanes run phase B)
+                elif capture:
+                    g = graphs[part, l] = torch.cuda.CUDAGraph()
+                    # phase B reads tensors phase A allocated (the trunk's activations, the cut's gradients): same memory pool
+                    pool = graphs['a', l].pool() if part == 'b' else None
+                    with torch.cuda.graph(g, stream=st, pool=pool, **cap):
+                        out[part] = parts[part](l)
+                else:
+                    with torch.cuda.stream(st):
+                        if mode == REPLAY:
+                            graphs[part, l].replay()
+                        else:
+                            out[part] = parts[part](l)
+        if capture:
+            torch.cuda.synchronize()
+            self._graph, self._graph_out = graphs, out['post']
+        return out.get('post'), out.get('a')
 
     # ------------------------------------------------------------------ data-parallel reduction (RCCL over xGMI)
     def _reduce_rest(self, captured=False):
@@ -523,7 +579,7 @@ class SWEMTrainer:
             # parity mode: drawn on the host (the global torch CPU generator, as the fixtures of the reference step were) and
             # sent through a ring of three pinned buffers -- a pageable copy would block the host until the previous step has
             # drained, i.e. serialise host and device every step
-            ring = self.__dict__.setdefault('_kappa_ring', {})
+            ring = self._kappa_ring
             if ring.get('shape') != tuple(bf['kappa0'].shape):
                 ring.update(shape=tuple(bf['kappa0'].shape), i=0, ev=[None] * 3,
                             pin=[torch.empty(bf['kappa0'].shape, dtype=torch.float32).pin_memory() for _ in range(3)])
@@ -537,7 +593,7 @@ class SWEMTrainer:
             ring['ev'][i].record()
         # mean over the clips of this rank and over the ranks (DistributedDataParallel averages, swem_trainer.py:41-43)
         world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
-        if getattr(self, '_gout_for', None) != (B, world, id(bf['gout'])):
+        if self._gout_for != (B, world, id(bf['gout'])):
             # a lane's loss vector is the mean over ITS clips: weight (its clips) / (clips of all lanes and ranks)
             chunks = self._lanes(B)['chunks']
             bf['gout'].copy_(torch.tensor([[float(b1 - b0) / (B * world), 0.0, 0.0] for b0, b1 in chunks]))
@@ -546,13 +602,12 @@ class SWEMTrainer:
         p, k = self.criterion.top_k(cur_iter, H * W)
         bf['k'].fill_(k)
         if self.use_graph and self._eager_steps >= 2 and self._graph is None and not ops.AUTOTUNE_PENDING():
-            self._capture(cur_iter)
+            self._step(CAPTURE, cur_iter)
         if self._graph is not None:
-            self._replay()
+            self._step(REPLAY)
             results, p = self._graph_out, (1.0 if p is None else p)
         else:
-            with self._math():
-                results, p = self._clips(cur_iter)
+            results, p = self._step(EAGER, cur_iter)
             self._eager_steps += 1
         # the step's fault flags, in stream order behind every launch of the step, into the message the loss scalars travel in:
         # after the all-reduce every rank holds "some rank faulted" and gates its optimizer launch on it ON THE DEVICE (ADVICE
@@ -576,8 +631,8 @@ class SWEMTrainer:
         # reference's trainer reads its losses -- a synchronisation -- every LOG_PERIOD steps anyway, basic_trainer.py:105-131), and
         # always on the eager first steps.  Nothing is lost in between: the fault word is sticky, so from the faulting step on
         # every optimizer launch finds the gate closed.
-        self._steps_seen = getattr(self, '_steps_seen', 0) + 1
-        every = getattr(self, 'fault_check_every', 20)
+        self._steps_seen += 1
+        every = self.fault_check_every
         if every and (self._graph is None or self._steps_seen % every == 0 or (self._foreign_fault and not sdist.active())):
             if self._look_at_faults() and not _redo:
                 return self.one_step(frames, init_mask, valid_obj, label, cur_iter, _redo=True)
@@ -598,7 +653,6 @@ class SWEMTrainer:
             trainer to the reference's own range (fp32 MFMA / bf16x6: modes (0, 1)), warns, and returns True: the caller redoes
             the step at hand (the batches of the skipped steps in between are lost, and counted in the warning);
             a trainer that is on the full-range modes already raises SwemRangeError (cannot happen: no fp16 pair is produced)."""
-        import warnings
         fl = self.buf['sums'][3:5].tolist()                 # (all-reduced: the same on every rank, and so is what follows)
         rng, other = fl[0] != 0.0, fl[1] != 0.0
         if not (rng or other):
@@ -612,7 +666,7 @@ class SWEMTrainer:
                                     'optimizer has not been stepped since the fault (%d steps skipped on every rank)'
                                     % (rng, other, bits | foreign, ops._fault_text((bits | foreign) & ~ops.FAULT_RANGE) or
                                        'raised on another rank', skipped))
-        modes = self.math_modes or ((2,) if self.amp else ((0, 1, 7) if self.f16x3 else (0, 1)))
+        modes = self.conv_modes()
         if 7 not in modes:
             raise ops.SwemRangeError('SWEM_FAULT_RANGE in a training step that runs no f16x3 launch (modes %s)' % (modes,))
         self.f16x3, self.math_modes = False, None
@@ -625,117 +679,21 @@ class SWEMTrainer:
                       RuntimeWarning)
         return True
 
+    def conv_modes(self):
+        """The conv math modes the step may run in: an explicit `math_modes`, else bf16 operands (2) under AMP, else the
+        fp32-level modes -- fp32 MFMA (0), bf16x6 (1) and, with `f16x3`, the fp16-pair arithmetic (7)."""
+        return self.math_modes or ((2,) if self.amp else ((0, 1, 7) if self.f16x3 else (0, 1)))
+
     def _math(self):
         """Conv math modes of the step: config.AMP = plain bf16 operands; otherwise the fp32-level modes only (fp32 MFMA,
         bf16x6 and -- round 5, `self.f16x3` -- the fp16-pair f16x3 with gradient maps scaled on the device, include/
         swem_hip_train.h) -- the 16-bit-operand bf16x3 mode the inference tuner may pick is kept out of the gradient path."""
-        import contextlib
         st = contextlib.ExitStack()
         st.enter_context(ops.use_book(self.book))
-        modes = self.math_modes or ((2,) if self.amp else ((0, 1, 7) if self.f16x3 else (0, 1)))
-        st.enter_context(ops.conv_math(modes))
+        st.enter_context(ops.conv_math(self.conv_modes()))
         # conv epilogues do not write operand planes here and the tuner keeps to the non-persistent kernel forms (ops.py,
         # TUNE_ROUND3_FORMS: measured on the four-lane step); the frozen-BN stages' own planes (autograd._planes_for) stay
         # (re-measured in round 4 with the step's timing stable to +-0.3 %: FUSE_SPLIT on or off is the same 112 / 69 clips/s --
         # round 3's "71 against 108" was the CPU-quota throttling of that round's processes, not the planes)
         st.enter_context(ops.flags(FUSE_SPLIT=False, TUNE_ROUND3_FORMS=False))
         return st
-
-    def _capture(self, cur_iter):
-        """One HIP graph per part: `_pre` and `_post` on the main stream, one graph per lane on the lane's own (probed)
-        stream.  A single graph with forked branches leaves the placement of the branches to the runtime, and two lanes on
-        one hardware queue serialise (measured: 40 to 56 clips/s from run to run); separate graphs replay on the streams
-        that `evaluator.overlapping_streams` found to overlap."""
-        torch.cuda.synchronize()
-        ls = self._lanes(self.buf['init_mask'].shape[0])
-        main = torch.cuda.current_stream()
-        # (scratch buffers of the captured launches are allocated inside the captures, ops.workspace: the eager warm-up
-        # steps left cached workspaces on these very streams, and a graph must not point into a cache entry that a later,
-        # larger eager request -- e.g. 480p validation between steps -- replaces)
-        cap = ops.graph_capture_kwargs()       # ("thread_local" while a process group's watchdog thread is alive: ops.py)
-        with self._math():
-            g_pre = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_pre, **cap):
-                self._pre()
-            packs, lanes_a, lanes_b = [], [], []
-            for l, st in enumerate(ls['streams']):
-                g = torch.cuda.CUDAGraph()
-                if st is None:
-                    with torch.cuda.graph(g, **cap):
-                        self._packs(l)
-                else:
-                    st.wait_stream(main)
-                    with torch.cuda.graph(g, stream=st, **cap):
-                        self._packs(l)
-                packs.append(g)
-            for st in ls['streams']:
-                if st is not None:
-                    main.wait_stream(st)
-            for l, st in enumerate(ls['streams']):
-                g = torch.cuda.CUDAGraph()
-                if st is None:
-                    with torch.cuda.graph(g, **cap):
-                        self._lane(l, cur_iter)
-                else:
-                    st.wait_stream(main)
-                    with torch.cuda.graph(g, stream=st, **cap):
-                        self._lane(l, cur_iter)
-                lanes_a.append(g)
-            g_rest = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_rest, **cap):
-                self._post_rest()
-                if self.reduce_in_graph:
-                    self._reduce_rest(captured=True)
-            for l, st in enumerate(ls['streams']):
-                # phase B reads tensors phase A allocated (the trunk's activations, the cut's gradients): same memory pool
-                g = torch.cuda.CUDAGraph()
-                if st is None:
-                    with torch.cuda.graph(g, pool=lanes_a[l].pool(), **cap):
-                        self._lane_trunk(l)
-                else:
-                    with torch.cuda.graph(g, stream=st, pool=lanes_a[l].pool(), **cap):
-                        self._lane_trunk(l)
-                lanes_b.append(g)
-            g_post = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_post, **cap):
-                out = self._post()
-        torch.cuda.synchronize()
-        self._graph, self._graph_out = (g_pre, packs, lanes_a, g_rest, lanes_b, g_post), out
-
-    def _replay(self):
-        g_pre, packs, lanes_a, g_rest, lanes_b, g_post = self._graph
-        ls = self._lane_state
-        main = torch.cuda.current_stream()
-        g_pre.replay()
-        for st, g in zip(ls['streams'], packs):            # the re-pack, a share per lane's stream
-            if st is None:
-                g.replay()
-            else:
-                st.wait_stream(main)
-                with torch.cuda.stream(st):
-                    g.replay()
-        for st in ls['streams']:
-            if st is not None:
-                main.wait_stream(st)                       # every pack is there before any lane reads one
-        for st, g in zip(ls['streams'], lanes_a):
-            if st is None:
-                g.replay()
-            else:
-                st.wait_stream(main)
-                with torch.cuda.stream(st):
-                    g.replay()
-        for st in ls['streams']:
-            if st is not None:
-                main.wait_stream(st)                       # phase A of every lane
-        g_rest.replay()
-        self._reduce_rest()                                # in flight while the lanes run phase B
-        for st, g in zip(ls['streams'], lanes_b):
-            if st is None:
-                g.replay()
-            else:
-                with torch.cuda.stream(st):
-                    g.replay()
-        for st in ls['streams']:
-            if st is not None:
-                main.wait_stream(st)
-        g_post.replay()

@@ -621,10 +621,13 @@ def _one_step_vs_reference(golden, tag, it, modes, lanes=None, wgrad_stream=None
         assert float(params[n].grad.abs().max()) == 0.0, n
 
 
-def test_graph_replay_equals_eager_steps(lib):
+@pytest.mark.parametrize('lanes', [None, 1])
+def test_graph_replay_equals_eager_steps(lib, lanes):
     """The captured step (HIP graph of all clips' forward/backward, replayed on static buffers with the bootstrap k, the
     random bases and the loss weight entering through device memory) gives the same losses and the same parameters as
-    eager steps, iteration after iteration (the kernels are deterministic: no atomics)."""
+    eager steps, iteration after iteration (the kernels are deterministic: no atomics).  lanes=None: the default, a lane
+    with a stream of its own per clip; lanes=1: both clips in the one lane on the caller's stream (captured without a
+    stream of its own, phase B's graph in phase A's pool, the weight gradients on the side stream)."""
     from swem_amd.train import SWEMTrainer
     tc = H.train_cases()
     case = dict(tc['cases']['r18'], hw=[128, 128])
@@ -634,7 +637,7 @@ def test_graph_replay_equals_eager_steps(lib):
     for mode in (False, True):
         model, _ = H.make_model_and_sd(cfg, case['wseed'], DEV, pred_scale=tc['pred_scale'])
         solver = dict(tc['solver_cfg'], BASE_LR=1e-4)        # a visible update per step
-        tr = SWEMTrainer(dict(SOLVER=solver, LOSS=tc['loss_cfg'], AMP=False), model, use_graph=mode)
+        tr = SWEMTrainer(dict(SOLVER=solver, LOSS=tc['loss_cfg'], AMP=False), model, use_graph=mode, lanes=lanes)
         torch.manual_seed(5)
         hist = []
         for it in (18, 19, 20, 45, 71, 5):                   # plain CE, annealed top-k, final top-k, plain again

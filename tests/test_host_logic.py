@@ -589,3 +589,51 @@ def test_lane_schedule_keeps_the_last_frame_out_of_the_graphs(binds):
                     assert (t - 1 in taken) == (pipelined and len(taken) > 0), tag
                     assert taken == list(range(2, t if pipelined else t - 1)) or (t <= 3 and taken == []), tag
                     assert len(tried) <= 1, tag
+
+
+def test_training_step_schedule():
+    """The order of a training step and its stream edges (train.step_schedule), which eager steps, capture and replay all walk:
+    written out for two lanes, and its shape for one, two and four."""
+    from swem_amd import train as T
+    M, LN, F, J, HO = T.MAIN, T.LANE, T.FORK, T.JOIN, T.HOST
+    assert len({M, LN, F, J, HO}) == 5
+    assert T.step_schedule(2) == [
+        (M, 'pre', None),
+        (F, None, 0), (F, None, 1), (LN, 'packs', 0), (LN, 'packs', 1), (J, None, 0), (J, None, 1),
+        (F, None, 0), (F, None, 1), (LN, 'a', 0), (LN, 'a', 1), (J, None, 0), (J, None, 1),
+        (M, 'rest', None), (HO, 'reduce_rest', None),
+        (LN, 'b', 0), (LN, 'b', 1), (J, None, 0), (J, None, 1),
+        (M, 'post', None)]
+    for n in (1, 2, 4):
+        s = T.step_schedule(n)
+        tag = (n, s)
+
+        def at(op):
+            assert s.count(op) == 1, (op, tag)
+            return s.index(op)
+
+        def between(kind, l, lo, hi):
+            return [i for i in range(lo + 1, hi) if s[i] == (kind, None, l)]
+        pre, rest, post = at((M, 'pre', None)), at((M, 'rest', None)), at((M, 'post', None))
+        assert pre < rest < post and [op for op in s if op[0] == M] == [s[pre], s[rest], s[post]], tag
+        host = at((HO, 'reduce_rest', None))
+        assert [op for op in s if op[0] == HO] == [s[host]], tag
+        lane_ops = [op for op in s if op[0] == LN]
+        assert sorted(lane_ops) == sorted((LN, part, l) for part in ('packs', 'a', 'b') for l in range(n)), tag
+        assert all(op[2] in range(n) for op in s if op[0] in (F, J)) and all(len(op) == 3 for op in s), tag
+        packs, a, b = ([at((LN, part, l)) for l in range(n)] for part in ('packs', 'a', 'b'))
+        for l in range(n):
+            assert pre < packs[l] < a[l] < rest < b[l] < post, tag
+            # a lane's packs and phase A each start behind a fork of their own from the last main operation before them (`pre`) ...
+            assert between(F, l, pre, packs[l]), tag
+            assert between(F, l, max(packs), a[l]), tag
+            # ... and phase B behind NO fork: only behind the same lane's phase A
+            assert not between(F, l, rest, b[l]), tag
+            # joined: after its packs before ANY lane's phase A, after phase A before `rest`, after phase B before `post`
+            assert between(J, l, packs[l], min(a)), tag
+            assert between(J, l, a[l], rest), tag
+            assert between(J, l, b[l], post), tag
+        # the forks of phase A come behind every join of the packs (a lane reads every lane's packs)
+        assert max(i for l in range(n) for i in between(J, l, packs[l], min(a))) < \
+            min(i for l in range(n) for i in between(F, l, max(packs), a[l])), tag
+        assert rest < host < min(b), tag

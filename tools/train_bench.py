@@ -126,8 +126,7 @@ def main():
         torch.cuda.synchronize()
         per_rank_clips = a.clips // world
         conv = fl.get('conv_fwd', 0.0) + fl.get('conv_dgrad', 0.0) + fl.get('conv_wgrad', 0.0)
-        modes = tr.math_modes or ((2,) if tr.amp else ((0, 1, 7) if tr.f16x3 else (0, 1)))
-        hist = tr.book.math_histogram(('math',) + tuple(modes))
+        hist = tr.book.math_histogram(('math',) + tuple(tr.conv_modes()))
         peak, pipe = (2500.0, 'bf16 (config.AMP: one MFMA product per useful product)') if a.amp else \
             ((2500.0 / 3, 'f16x3 (three fp16 MFMA products per useful product)') if hist.get('f16x3', 0) >= max(hist.get('bf16x6', 0), 1)
              else (2500.0 / 6, 'bf16x6 (six bf16 MFMA products per useful product)'))
