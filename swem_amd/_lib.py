@@ -1,4 +1,5 @@
-"""ctypes binding of libswem_hip.so (C ABI: include/swem_hip.h, swem_hip_train.h, swem_hip_metrics.h, swem_hip_data.h).
+"""ctypes binding of libswem_hip.so (C ABI: include/swem_hip.h, swem_hip_train.h, swem_hip_metrics.h, swem_hip_data.h,
+swem_hip_io.h).
 
 There is no CPU fallback: if the library is missing or a call fails this module raises.
 Build the library with ``python -m swem_amd.build`` (or ``__graft_entry__.build()``).
@@ -10,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SWEM_HIP_LIB: another build of the same library -- the debug / tuning builds the tools make, e.g. tools/conv_stamps.py)
 LIB_PATH = os.environ.get('SWEM_HIP_LIB') or os.path.join(_HERE, 'libswem_hip.so')
 
-_p, _i, _ll, _f, _sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
+_p, _i, _ll, _f, _sz, _d = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes).  Must list every symbol include/swem_hip.h declares
 # (tests/test_abi.py cross-checks against the header).
@@ -132,6 +133,12 @@ SIGNATURES = {
     'swem_augment_static_u8': (_i, [_p] * 9 + [_i] * 7 + [_p, _sz]),
     'swem_synth_workspace': (_sz, [_i, _i, _i]),
     'swem_synth_frames_u8': (_i, [_p] * 6 + [_i] * 5 + [_p, _sz]),
+    # ---- include/swem_hip_io.h
+    'swem_stage_frames_u8': (_i, [_p, _p, _p, _i, _i, _i, _i, _i]),
+    'swem_labels_onehot_u8': (_i, [_p, _p, _p, _p, _i, _i, _i]),
+    'swem_pack_u8_lut_i64': (_i, [_p, _p, _p, _ll, _p, _i]),
+    'swem_overlay_workspace': (_sz, [_i]),
+    'swem_overlay_u8': (_i, [_p, _p, _p, _p, _d, _d, _p, _i, _i, _i, _p, _sz]),
 }
 
 _lib = None

@@ -5,7 +5,13 @@ utils/visualization.py:40-43).
 * ``IndexMapWriter``: predicted int64 index maps -> uint8 on the device (8x less PCIe traffic), asynchronous copy into
   pinned host memory on a side stream, palette-PNG encoding (``save_seg_mask``) on a small thread pool so that neither the
   copy nor the zlib work sits between two sequences.
-Nothing here touches the model; the dataset classes of the reference stay out of scope.
+* ``davis_sequence_u8`` / ``ytvos_sequence_u8``: the same staging FROM DECODED BYTES (include/swem_hip_io.h, csrc/stage.hip):
+  uint8 RGB frames and palette-PNG index maps are uploaded as they are; b / 255, HWC -> CHW, the bicubic resize and the one-hot
+  annotations (datasets/DAVIS_Test.py:40-49, datasets/YTVOS_Test.py:116-132) happen on the device.  The tables and the
+  YouTube-VOS input size (YTVOS_Test.py:14-19, 75-91) are restated here; reading the files stays with the caller.
+* ``IndexMapWriter`` also maps indices to object ids (basic_evaluator.py:202-206) and writes the overlay pictures of
+  VAL.VISUALIZE (utils/visualization.py:46-72, basic_evaluator.py:185-196, 241-265), both on the device.
+Nothing here touches the model.
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -23,6 +29,144 @@ def stage_sequence(frames, masks, size=(480, 864)):
     in_masks = [None] * frames.shape[1]
     in_masks[0] = masks[:, 0].float()
     return in_frames, in_masks
+
+
+def get_suit_size(size, ratio=16):
+    """YTVOS_Test.py:14-19: to the nearer multiple of 16 (the reference adds 16, whatever `ratio`; it only ever passes 16)."""
+    r = size % ratio
+    size -= r
+    if r > 7:
+        size += 16
+    return size
+
+
+def ytvos_input_size(h, w, short_size=495):
+    """YTVOS_Test.py:27, 75-91: the size a YouTube-VOS clip of h x w frames is fed at -- the shorter side at most
+    get_suit_size(short_size) = 496, both sides multiples of 16.  720x1280 -> (496, 880)."""
+    h, w = int(h), int(w)
+    ssize = get_suit_size(int(short_size))
+    if h < w:
+        if h < ssize:
+            return get_suit_size(h), get_suit_size(w)
+        out_h = ssize
+        return out_h, get_suit_size(get_suit_size(int(w * out_h / h)))
+    if w < ssize:
+        return get_suit_size(h), get_suit_size(w)
+    out_w = ssize
+    return get_suit_size(int(h * out_w / w)), out_w
+
+
+def _labels_present(label_u8):
+    """bool[256]: which labels a uint8 map holds (host array or device tensor; 256 flags come back, never the pixels)."""
+    if isinstance(label_u8, torch.Tensor):
+        if label_u8.dtype != torch.uint8:
+            raise TypeError('label maps are uint8, got %s' % label_u8.dtype)
+        return (torch.bincount(label_u8.reshape(-1).long(), minlength=256) > 0).cpu().numpy()
+    a = np.asarray(label_u8)
+    if a.dtype != np.uint8:
+        raise TypeError('label maps are uint8, got %s' % a.dtype)
+    return np.bincount(a.reshape(-1), minlength=256) > 0
+
+
+def davis_table(first_label, single_obj=False):
+    """The channel table of a DAVIS first-frame annotation and its channel count: (table uint8[256], obj_n).
+    DAVIS_Test.py:43-48 -> data_utils.py:141-186 (to_onehot_tensor, shuffle=False): obj_n = largest label + 1 channels; the ids
+    that are present take channels 1.. in ascending order (compacted: with labels {0,1,3} id 3 is channel 2 and channel 3 stays
+    empty); every other label lands in channel 0, which the reference computes as 1 - sum.  single_obj: every label > 1 is label 1
+    (DAVIS_Test.py:43-44)."""
+    present = _labels_present(first_label).copy()
+    if single_obj and present[2:].any():
+        present[1] = True
+        present[2:] = False
+    ids = [int(i) for i in np.nonzero(present)[0] if i > 0]
+    obj_n = (max(ids) if ids else 0) + 1
+    if obj_n > 255:
+        raise ValueError('davis_table: label 255 in the annotation would need 256 channels (255 at the most)')
+    table = np.zeros(256, np.uint8)
+    for k, i in enumerate(ids):
+        table[i] = k + 1
+    if single_obj:
+        table[2:] = table[1]
+    return table, obj_n
+
+
+def ytvos_table(ids):
+    """The channel table of a YouTube-VOS annotation frame that introduces the objects `ids` (YTVOS_Test.py:124-130): label 0 ->
+    channel 0, ids[k] -> channel k + 1, every other label (an object annotated earlier) -> no channel (255)."""
+    ids = [int(i) for i in ids]
+    if len(ids) > 254 or len(set(ids)) != len(ids) or any(not 0 < i < 256 for i in ids):
+        raise ValueError('ytvos_table: need at most 254 distinct object ids in 1..255, got %s' % (ids,))
+    table = np.full(256, 255, np.uint8)
+    table[0] = 0
+    for k, i in enumerate(ids):
+        table[i] = k + 1
+    return table
+
+
+def ytvos_id_table(ann):
+    """obj_idx_list of YTVOS_Test.py:117-128 for ann = {frame_idx: (label_u8, ids)}: 0, then the ids in frame order and in
+    list order within a frame -- index k of the evaluator's maps is object id table[k] (basic_evaluator.py:202-206)."""
+    out = [0]
+    for frame_idx in sorted(ann):
+        out += [int(i) for i in ann[frame_idx][1]]
+    if len(out) > 256 or any(not 0 <= i < 256 for i in out):
+        raise ValueError('ytvos_id_table: object ids are bytes and at most 255 objects, got %s' % (out,))
+    return np.asarray(out, np.uint8)
+
+
+def _device_u8(x, device=None):
+    """uint8 bytes on the device: a device tensor as it is, a numpy array / host tensor uploaded once from pinned memory."""
+    if isinstance(x, torch.Tensor) and x.is_cuda:
+        if x.dtype != torch.uint8:
+            raise TypeError('decoded frames and label maps are uint8, got %s' % x.dtype)
+        return x.contiguous()
+    host = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    if host.dtype != torch.uint8:
+        raise TypeError('decoded frames and label maps are uint8, got %s' % host.dtype)
+    pinned = torch.empty(host.shape, dtype=torch.uint8, pin_memory=True)
+    pinned.copy_(host)
+    return pinned.to('cuda' if device is None else device, non_blocking=True)
+
+
+def davis_sequence_u8(frames_u8, first_label_u8, single_obj=False, size=(480, 864)):
+    """DAVIS_Test.__getitem__ + basic_evaluator.py:157-163 from decoded bytes: frames_u8 (T,H,W,3) uint8 RGB, first_label_u8
+    (H,W) uint8 palette indices -> (in_frames (1,T,3,480,864) fp32, in_masks with the (1,obj_n,H,W) fp32 first-frame mask,
+    obj_n): what `evaluate_davis_seq` takes.  The mask stays at the source size, as in `stage_sequence`."""
+    fr = _device_u8(frames_u8)
+    lab = _device_u8(first_label_u8, fr.device)
+    table, obj_n = davis_table(first_label_u8, single_obj)
+    in_frames = ops.stage_frames_u8(fr, tuple(size)).unsqueeze(0)
+    in_masks = [None] * fr.shape[0]
+    in_masks[0] = ops.labels_onehot_u8(lab, table, obj_n).unsqueeze(0)
+    return in_frames, in_masks, obj_n
+
+
+def ytvos_sequence_u8(frames_u8, ann, short_size=495):
+    """YTVOS_Test.__getitem__ from decoded bytes: frames_u8 (T,H,W,3) uint8 RGB from the first annotated frame on,
+    ann = {frame_idx: (label_u8 (H,W), ids)} with the objects each annotation frame introduces -> (in_frames
+    (1,T,3,out_h,out_w) fp32 at `ytvos_input_size`, init_masks with a (1,len(ids)+1,H,W) fp32 mask at every annotation frame,
+    id_table): what `evaluate_ytvos_seq` takes (out_size = the frames' own H, W) and what `IndexMapWriter.submit(id_table=)`
+    maps the results with."""
+    if 0 not in ann:
+        raise ValueError('ytvos_sequence_u8: the clip starts at its first annotated frame (ann[0] is missing)')
+    fr = _device_u8(frames_u8)
+    T, H, W = fr.shape[:3]
+    id_table = ytvos_id_table(ann)
+    in_frames = ops.stage_frames_u8(fr, ytvos_input_size(H, W, short_size)).unsqueeze(0)
+    init_masks = [None] * T
+    for frame_idx in sorted(ann):
+        label, ids = ann[frame_idx]
+        lab = _device_u8(label, fr.device)
+        if tuple(lab.shape) != (H, W):
+            raise ValueError('ytvos_sequence_u8: annotation %d is %s, the frames are %s' % (frame_idx, tuple(lab.shape), (H, W)))
+        init_masks[frame_idx] = ops.labels_onehot_u8(lab, ytvos_table(ids), len(ids) + 1).unsqueeze(0)
+    return in_frames, init_masks, id_table
+
+
+def save_rgb(img, path):
+    """(H,W,3) uint8 RGB -> PNG (the overlay pictures; the reference's cv2.imwrite of the BGR array)."""
+    from PIL import Image
+    Image.fromarray(img, 'RGB').save(path)
 
 
 def save_seg_mask(pred, seg_path, palette):
@@ -49,42 +193,86 @@ def default_palette(n=256):
 
 
 class IndexMapWriter:
-    def __init__(self, out_dir, palette=None, workers=4):
+    def __init__(self, out_dir, palette=None, workers=4, overlay_alpha=0.4):
         self.out_dir = out_dir
         self.palette = default_palette() if palette is None else palette
+        self.overlay_alpha = overlay_alpha
         self.pool = ThreadPoolExecutor(max_workers=workers)
         self.copy_stream = torch.cuda.Stream() if torch.cuda.is_available() else None
         self.pending = []
 
-    def submit(self, seq_name, preds, first_index=1):
-        """preds: list of (1,H,W) int64 device index maps of one sequence (frames first_index, first_index+1, ...).
-        Returns immediately; files appear as ``out_dir/seq_name/%05d.png``."""
-        d = os.path.join(self.out_dir, seq_name)
-        os.makedirs(d, exist_ok=True)
-        stacked = torch.cat(preds, dim=0).contiguous()                 # (T-1,H,W) int64, device
-        u8 = ops.pack_u8(stacked)
-        host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
+    def _palette768(self):
+        pal = np.zeros(768, np.uint8)
+        flat = np.asarray(self.palette, np.uint8).reshape(-1)[:768]
+        pal[:flat.size] = flat
+        return pal
+
+    def _to_host(self, tensors):
+        """Asynchronous copies into pinned memory on the copy stream; (host tensors, event)."""
+        hosts = [torch.empty(t.shape, dtype=torch.uint8, pin_memory=True) for t in tensors]
         ev = torch.cuda.Event()
         self.copy_stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.copy_stream):
-            host.copy_(u8, non_blocking=True)
+            for h, t in zip(hosts, tensors):
+                h.copy_(t, non_blocking=True)
             ev.record()
-        u8.record_stream(self.copy_stream)
+        for t in tensors:
+            t.record_stream(self.copy_stream)
+        return hosts, ev
+
+    def _overlay(self, frames_u8, u8, device):
+        fr = _device_u8(frames_u8, device)
+        if tuple(fr.shape) != tuple(u8.shape) + (3,):
+            raise ValueError('overlay frames are %s, the index maps %s' % (tuple(fr.shape), tuple(u8.shape)))
+        return ops.overlay_u8(fr, u8, self._palette768(), self.overlay_alpha)
+
+    def submit(self, seq_name, preds, first_index=1, id_table=None, names=None, keep=None, overlay_frames_u8=None):
+        """preds: list of (1,H,W) int64 device index maps of one sequence (frames first_index, first_index+1, ...).
+        Returns immediately; files appear as ``out_dir/seq_name/%05d.png``.
+          id_table : index k is written as object id id_table[k] (basic_evaluator.py:202-206; `ytvos_id_table`)
+          names    : the basenames of the sequence's frames, indexed by frame number: frame t is ``names[t].png``
+          keep     : write only the index maps whose basename (or frame number, without `names`) is in it
+                     (basename_to_save, basic_evaluator.py:258); overlays are written for every frame, as the reference does
+          overlay_frames_u8 : the decoded (T,H,W,3) uint8 RGB frames of the whole sequence at the maps' size, indexed by frame
+                     number (host or device): also writes ``out_dir/overlay/seq_name/<same name>.png``"""
+        d = os.path.join(self.out_dir, seq_name)
+        os.makedirs(d, exist_ok=True)
+        stacked = torch.cat(preds, dim=0).contiguous()                 # (T-1,H,W) int64, device
+        n = stacked.shape[0]
+        u8 = ops.pack_u8(stacked) if id_table is None else ops.pack_u8_lut(stacked, id_table)
+        tensors, od = [u8], None
+        if overlay_frames_u8 is not None:
+            od = os.path.join(self.out_dir, 'overlay', seq_name)
+            os.makedirs(od, exist_ok=True)
+            tensors.append(self._overlay(overlay_frames_u8[first_index:first_index + n], u8, u8.device))
+        hosts, ev = self._to_host(tensors)
+        stems = [('%05d' % (first_index + t)) if names is None else names[first_index + t] for t in range(n)]
+        kept = [keep is None or (stems[t] if names is not None else first_index + t) in keep for t in range(n)]
 
         def write():
             ev.synchronize()
-            arr = host.numpy()
-            for t in range(arr.shape[0]):
-                save_seg_mask(arr[t], os.path.join(d, '%05d.png' % (first_index + t)), self.palette)
-            return arr.shape[0]
+            arr = hosts[0].numpy()
+            for t in range(n):
+                if kept[t]:
+                    save_seg_mask(arr[t], os.path.join(d, stems[t] + '.png'), self.palette)
+                if od is not None:
+                    save_rgb(hosts[1].numpy()[t], os.path.join(od, stems[t] + '.png'))
+            return sum(kept)
         self.pending.append(self.pool.submit(write))
 
-    def save_first(self, seq_name, mask_onehot):
-        """Frame 0's given annotation (basic_evaluator.py:180-182)."""
+    def save_first(self, seq_name, mask_onehot, id_table=None, name=None, overlay_frame_u8=None):
+        """Frame 0's given annotation (basic_evaluator.py:180-187, 238-244); `id_table`, `name` and the (H,W,3) uint8
+        `overlay_frame_u8` as in `submit`."""
         d = os.path.join(self.out_dir, seq_name)
         os.makedirs(d, exist_ok=True)
+        stem = '00000' if name is None else name
         idx, _ = ops.argmax_onehot(mask_onehot.float().contiguous(), want_onehot=False)
-        save_seg_mask(ops.pack_u8(idx).cpu().numpy()[0], os.path.join(d, '00000.png'), self.palette)
+        u8 = ops.pack_u8(idx) if id_table is None else ops.pack_u8_lut(idx, id_table)
+        save_seg_mask(u8.cpu().numpy()[0], os.path.join(d, stem + '.png'), self.palette)
+        if overlay_frame_u8 is not None:
+            od = os.path.join(self.out_dir, 'overlay', seq_name)
+            os.makedirs(od, exist_ok=True)
+            save_rgb(self._overlay(overlay_frame_u8[None], u8, u8.device).cpu().numpy()[0], os.path.join(od, stem + '.png'))
 
     def close(self):
         n = sum(f.result() for f in self.pending)

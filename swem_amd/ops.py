@@ -1617,6 +1617,75 @@ def pack_u8(idx):
     return out
 
 
+def _chk_u8(t, name, ndim):
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == ndim):
+        raise _lib.SwemHipError('%s: need a contiguous %d-d uint8 device tensor (got %s %s %s)'
+                                % (name, ndim, t.device, t.dtype, tuple(t.shape)))
+    return t
+
+
+def _table_bytes(table, n, name):
+    """A small host table (numpy array, list, bytes) as `n` bytes for a by-value launch argument."""
+    import numpy as np
+    b = np.ascontiguousarray(np.asarray(table.cpu() if isinstance(table, torch.Tensor) else table).astype(np.uint8, casting='unsafe')).tobytes()
+    if len(b) != n:
+        raise _lib.SwemHipError('%s: the table holds %d entries, not %d' % (name, len(b), n))
+    return b
+
+
+def stage_frames_u8(frames_u8, size):
+    """swem_stage_frames_u8 (include/swem_hip_io.h): (T,Hs,Ws,3) uint8 RGB on the device -> (T,3,Ho,Wo) fp32 in [0,1], b / 255
+    then the bicubic resize of `resize_planes`."""
+    _chk_u8(frames_u8, 'stage_frames_u8', 4)
+    T, Hs, Ws, ch = frames_u8.shape
+    if ch != 3:
+        raise _lib.SwemHipError('stage_frames_u8: frames are (T,H,W,3) RGB, got %s' % (tuple(frames_u8.shape),))
+    out = torch.empty((T, 3, int(size[0]), int(size[1])), dtype=torch.float32, device=frames_u8.device)
+    _lib.call('swem_stage_frames_u8', _stream(), frames_u8.data_ptr(), out.data_ptr(), T, Hs, Ws, int(size[0]), int(size[1]))
+    return out
+
+
+def labels_onehot_u8(label_u8, chan_table, channels):
+    """swem_labels_onehot_u8: (H,W) uint8 index map on the device + a 256-entry host table label -> channel (255: none) ->
+    (channels,H,W) fp32 one-hot."""
+    _chk_u8(label_u8, 'labels_onehot_u8', 2)
+    H, W = label_u8.shape
+    out = torch.empty((int(channels), H, W), dtype=torch.float32, device=label_u8.device)
+    _lib.call('swem_labels_onehot_u8', _stream(), label_u8.data_ptr(), _table_bytes(chan_table, 256, 'labels_onehot_u8'),
+              out.data_ptr(), int(channels), H, W)
+    return out
+
+
+def pack_u8_lut(idx, id_table):
+    """swem_pack_u8_lut_i64: int64 index maps -> uint8 object ids `id_table[idx]` on the device (0 beyond the table):
+    basic_evaluator.py:202-206 fused with `pack_u8`."""
+    if not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous()):
+        raise _lib.SwemHipError('pack_u8_lut: need a contiguous int64 device tensor')
+    n_ids = len(id_table)
+    out = torch.empty(idx.shape, dtype=torch.uint8, device=idx.device)
+    _lib.call('swem_pack_u8_lut_i64', _stream(), idx.data_ptr(), out.data_ptr(), idx.numel(),
+              _table_bytes(id_table, n_ids, 'pack_u8_lut'), n_ids)
+    return out
+
+
+def overlay_u8(frames_u8, labels_u8, palette, alpha=0.4):
+    """swem_overlay_u8: (T,H,W,3) uint8 RGB frames + (T,H,W) uint8 index maps + a 256x3 RGB palette -> (T,H,W,3) uint8 overlay
+    pictures (utils/visualization.py:46-72)."""
+    _chk_u8(frames_u8, 'overlay_u8 frames', 4)
+    _chk_u8(labels_u8, 'overlay_u8 labels', 3)
+    T, H, W, ch = frames_u8.shape
+    if ch != 3 or tuple(labels_u8.shape) != (T, H, W) or labels_u8.device != frames_u8.device:
+        raise _lib.SwemHipError('overlay_u8: frames (T,H,W,3) and labels (T,H,W) on one device, got %s and %s'
+                                % (tuple(frames_u8.shape), tuple(labels_u8.shape)))
+    out = torch.empty_like(frames_u8)
+    nbytes = _lib.query('swem_overlay_workspace', T)
+    ws = workspace(nbytes, frames_u8.device)
+    alpha = float(alpha)
+    _lib.call('swem_overlay_u8', _stream(), frames_u8.data_ptr(), labels_u8.data_ptr(), _table_bytes(palette, 768, 'overlay_u8'),
+              alpha, 1.0 - alpha, out.data_ptr(), T, H, W, ws.data_ptr(), nbytes)
+    return out
+
+
 def transpose(x, ld=None):
     """(batch, R, Cc) -> (batch, Cc, ld) with zero padded columns."""
     _chk(x)
