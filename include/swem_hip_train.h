@@ -197,9 +197,12 @@ int swem_prep_value_input_bwd_f32(void *stream, const float *dxin, float *dmasks
 /* ------------------------------------------------------------------------------------
  * EM / matching in the training step.  The E, M and W steps run under no_grad in the reference (modules.py:93,112,122):
  * only the value update nu = (zita_prev*nu_prev + v.z)/zita (:164-165) and the matching carry gradient.
- * swem_memorize_train_f32 = swem_memorize_f32 that also returns the last responsibilities z [N][Pz][2L]
- * (Pz = swem_em_pad(P), rows >= P zero) for swem_nu_update_bwd_f32:
- *   dv [N][P][V] (the NHWC value map's gradient), dnu_prev [2N][V][L] (may be NULL) from dnu [2N][V][L] */
+ * swem_memorize_train_f32 = swem_memorize_f32 (kappa_out, nu_out, zita_out bit for bit) that also returns the last
+ * responsibilities z [N][Pz][2L] (Pz = swem_em_pad(P); every row is written: rows >= P are zero whatever z_out held) --
+ * the z that nu_out was made from -- for swem_nu_update_bwd_f32:
+ *   dv [N][P][V] (the NHWC value map's gradient), dnu_prev [2N][V][L] (may be NULL) from dnu [2N][V][L]
+ *   V % 4 == 0 and L % 32 == 0 (L = 32 included: the backward takes more L than swem_memorize_train_f32, which wants
+ *   L = 64, 128 or 256); the workspace's contents on entry are irrelevant. */
 int swem_memorize_train_f32(void *stream, const float *x, const float *v, const float *masks, const float *kappa_prev,
                             const float *nu_prev, const float *zita_prev, float *kappa_out, float *nu_out,
                             float *zita_out, float *z_out, int N, int C, int V, int P, int L, int T, float tau,
@@ -209,7 +212,12 @@ int swem_nu_update_bwd_f32(void *stream, const float *z, const float *zita_prev,
                            float *dv, float *dnu_prev, int N, int V, int P, int L, void *ws, size_t ws_bytes);
 /* backward of swem_match_f32 for the N <= 7 objects of one clip: dmem [N][Pm][V] and dS [N][P][2*topl] (dS may be NULL)
  * -> dqk [P][C] (summed over objects; through the query's l2norm), dnu_first / dnu_update [N][2][V][L].
- * Ties among the top-l values take the gradient jointly (measure zero). */
+ * Ties among the top-l values take the gradient jointly (measure zero).
+ *   dmem: only rows < P are used; rows [P, Pm) (Pm = swem_match_pad(P)) may hold any finite values.
+ *   Shapes: those swem_match_f32 takes -- C = 64 or 128, nbanks * L = 64, 128, 256 or 512, V any multiple of 4 (V = 4 is the
+ *   smallest), 1 <= topl <= 64, tau > 0, 1 <= N <= 7.  Anything else, a half-given update bank (kappa_update, nu_update and
+ *   dnu_update are all NULL or all given) and a workspace that is too small are refused before the first launch: no output
+ *   is written.  The workspace's contents on entry are irrelevant. */
 size_t swem_match_bwd_workspace(int N, int C, int V, int P, int L, int nbanks);
 int swem_match_bwd_f32(void *stream, const float *qk, const float *kappa_first, const float *nu_first,
                        const float *kappa_update, const float *nu_update, const float *dmem, const float *dS,

@@ -792,6 +792,10 @@ extern "C" int swem_match_bwd_f32(void *stream, const float *qk, const float *ka
   SWEM_REQUIRE(N >= 1 && N <= 7, SWEM_E_SHAPE, "match_bwd: 1..7 objects per clip (got %d)", N);
   const int nbanks = kappa_update ? 2 : 1;
   const int Lm = nbanks * L, Ltot = 2 * Lm, Pm = swem_match_pad(P);
+  int rc;
+  // what the forward refuses, the backward refuses too, before its first launch (topl > 64 would index past the pixel
+  // kernel's 64-entry rank list, an Lm outside the four instances would run the Lm = 512 one)
+  if ((rc = match_check(C, V, L, Lm, topl, tau))) return rc;
   MatchBwdWs w = match_bwd_ws(N, C, V, P, L, nbanks);
   SWEM_REQUIRE(ws && ws_bytes >= w.total, SWEM_E_WORKSPACE, "match_bwd: workspace %zu < %zu", ws_bytes, w.total);
   char *base = static_cast<char *>(ws);
@@ -801,7 +805,6 @@ extern "C" int swem_match_bwd_f32(void *stream, const float *qk, const float *ka
   float *mkn = (float *)(fb + fw.mkn), *mvp = (float *)(fb + fw.mvp), *pT = (float *)(fb + fw.pT);
   float *mvpT = (float *)(base + w.mvpT), *dP = (float *)(base + w.dP), *mknT = (float *)(base + w.mknT);
   float *dmvp = (float *)(base + w.dmvp), *dqn = (float *)(base + w.dqn);
-  int rc;
   // packed keys twice: raw for the affinity kernel (it normalises, exactly as in the forward), normalised for the d qn GEMM
   float *mknn = (float *)(base + w.mknn);
   if ((rc = swem_norm_bases_into(stream, kappa_first, mkn, 2 * N, C, L, Lm, 0, 0))) return rc;
