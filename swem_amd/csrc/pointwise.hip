@@ -1237,6 +1237,12 @@ static int cbam_impl(void *stream, const float *x, const float *w1, const float 
   SWEM_REQUIRE(x && w1 && b1 && w2 && b2 && w7 && b7 && cscale && y, SWEM_E_ARG, "cbam: null pointer");
   SWEM_REQUIRE(C % 4 == 0 && C <= 4096 && hid > 0 && hid <= 256, SWEM_E_SHAPE, "cbam: unsupported C/hid");
   SWEM_REQUIRE(ws && ws_bytes >= swem_cbam_workspace(B, H, W, C), SWEM_E_WORKSPACE, "cbam: workspace too small");
+  // (the plane arguments are refused before the first launch, so that a refused call has written nothing: cscale is an output)
+  if (planes || planes_relu) {
+    SWEM_REQUIRE(C % 8 == 0, SWEM_E_SHAPE, "cbam_planes: need C %% 8 == 0");
+    SWEM_REQUIRE((!planes || (nplanes >= 2 && nplanes <= 4)) && (!planes_relu || (nplanes_relu >= 2 && nplanes_relu <= 4)),
+                 SWEM_E_ARG, "cbam_planes: 2 or 3 planes per variant");
+  }
   const int P = H * W;
   float *part = static_cast<float *>(ws);
   float *comp = part + (size_t)B * CBAM_CHUNKS * 2 * C;
@@ -1258,9 +1264,6 @@ static int cbam_impl(void *stream, const float *x, const float *w1, const float 
   hipLaunchKernelGGL(cbam_sgate_kernel, grid1((long long)B * P), dim3(256), 0, ST, comp, w7, b7, sg, B, H, W);
   SWEM_CHECK_LAUNCH("cbam_sgate");
   if (planes || planes_relu) {
-    SWEM_REQUIRE(C % 8 == 0, SWEM_E_SHAPE, "cbam_planes: need C %% 8 == 0");
-    SWEM_REQUIRE((!planes || (nplanes >= 2 && nplanes <= 4)) && (!planes_relu || (nplanes_relu >= 2 && nplanes_relu <= 4)),
-                 SWEM_E_ARG, "cbam_planes: 2 or 3 planes per variant");
     hipLaunchKernelGGL(cbam_apply_planes_kernel, dim3((unsigned)cdiv((long long)B * P, 32), (unsigned)cdiv(C / 8, 8)),
                        dim3(256), 0, ST, x, cscale, sg, y, static_cast<unsigned short *>(planes), nplanes,
                        static_cast<unsigned short *>(planes_relu), nplanes_relu, B, P, C, static_cast<unsigned *>(fault));

@@ -93,12 +93,15 @@ def ulps(got, want64):
 
 class Sweep:
     """Collects what a sweep measures (floats: the worst over the cases, wanted <= bar * shrink; bools: wanted True), records it,
-    then fails with every case that missed.  shrink = 0.25 for the fp32 stand-ins."""
+    then fails with every case that missed.  shrink = 0.25 for the fp32 stand-ins.  bars / prefix: another module's table of
+    bars and the prefix of its parity records (tests/test_gpu_frame_edges.py)."""
 
-    def __init__(self, key, shrink=1.0):
+    def __init__(self, key, shrink=1.0, bars=None, prefix='train_edges/'):
         self.key, self.shrink, self.worst, self.bad = key, shrink, {}, {}
+        self.bars, self.prefix = BARS if bars is None else bars, prefix
 
     def add(self, case, name, value, bar=None, shrink=None, standin=None):
+        BARS = self.bars
         if isinstance(value, bool):
             self.worst[name] = self.worst.get(name, True) and value
             fail = not value
@@ -117,7 +120,7 @@ class Sweep:
     def finish(self, record=True):
         print('%s: %s' % (self.key, self.worst))
         if record:
-            H.record_parity('train_edges/' + self.key, self.worst)
+            H.record_parity(self.prefix + self.key, self.worst)
         assert not self.bad, self.bad
 
 
