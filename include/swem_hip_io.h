@@ -1,5 +1,6 @@
 /*
- * swem_hip_io.h -- C ABI of libswem_hip.so, evaluation staging part: decoded bytes in, result bytes out (csrc/stage.hip).
+ * swem_hip_io.h -- C ABI of libswem_hip.so, evaluation staging part: decoded bytes in, result bytes out (csrc/stage.hip), result
+ * PNG files out (csrc/png.hip).
  * Conventions, error codes and swem_last_error(): swem_hip.h.
  *
  * The reference's evaluation loop does this work on the host, a frame at a time: its dataset classes turn every decoded JPEG
@@ -54,6 +55,34 @@ int swem_pack_u8_lut_i64(void *stream, const long long *x, unsigned char *y, lon
 size_t swem_overlay_workspace(int T);
 int swem_overlay_u8(void *stream, const unsigned char *frames, const unsigned char *labels, const unsigned char *palette768,
                     double alpha, double one_minus_alpha, unsigned char *out, int T, int H, int W, void *ws, size_t ws_bytes);
+
+/* utils/visualization.py:40-43 (save_seg_mask: Image.fromarray, putpalette, save) as the evaluator calls it for every result
+ * frame (basic_evaluator.py:177-192, 254-260), without the host: T index maps in, T complete PNG files out (csrc/png.hip,
+ * DESIGN.md section 11).  Scanlines use filter type 0; the deflate stream is cut into segments of up to 16 whole scanlines (at
+ * most 65535 bytes), each coded on its own with literals and matches at distance 1 under the fixed Huffman codes, or as a
+ * stored block where that is shorter, ended on a byte boundary and carried by an IDAT chunk of its own.  Any PNG reader
+ * decodes the files to the maps, byte for byte; they are larger than zlib's.
+ *
+ * The largest file a H x W map can give: every segment stored, plus the headers --
+ *   8 + 25 + 780 (signature, IHDR, PLTE) + 2 (zlib header) + H * (W + 1) + 17 * nseg (a stored block's 5 bytes and a chunk's 12)
+ *   + 21 + 12 (closing IDAT with the final empty block and the Adler-32, IEND),
+ *   nseg = ceil(H / min(16, floor(65535 / (W + 1)))).
+ * 0 for a shape the encoder refuses (H < 1, W < 1, W + 1 > 65535). */
+size_t swem_png_capacity(int H, int W);
+/* basic_evaluator.py:177-192, 254-260: the scratch of one call on T frames (segment slots and their lengths / checksums) */
+size_t swem_png_workspace(int T, int H, int W);
+/* visualization.py:40-43 for the T maps of basic_evaluator.py:177-192, 254-260 in three launches (encode, offsets, pack).
+ *   maps       : [T][H][W] uint8 (device)
+ *   palette768 : 256 x 3 uint8 RGB (HOST) -> colour type 3 with a 256-entry PLTE; NULL -> colour type 0 (grayscale), no PLTE:
+ *                save_seg_mask(palette=None)
+ *   blob       : blob_bytes >= T * swem_png_capacity(H, W) (device): the T files back to back, file t = blob[offsets[t] ..
+ *                offsets[t + 1])
+ *   offsets    : T + 1 int64 (device, 8-byte aligned); offsets[0] = 0, offsets[T] = the bytes to copy to the host
+ *   ws         : swem_png_workspace(T, H, W) bytes, 16-byte aligned
+ * 1 <= T <= 65535.  A blob or workspace below those sizes is refused (SWEM_E_WORKSPACE) before anything is launched: the
+ * kernels cannot write past either. */
+int swem_png_encode_u8(void *stream, const unsigned char *maps, const unsigned char *palette768, unsigned char *blob,
+                       size_t blob_bytes, long long *offsets, int T, int H, int W, void *ws, size_t ws_bytes);
 
 #ifdef __cplusplus
 }

@@ -139,6 +139,9 @@ SIGNATURES = {
     'swem_pack_u8_lut_i64': (_i, [_p, _p, _p, _ll, _p, _i]),
     'swem_overlay_workspace': (_sz, [_i]),
     'swem_overlay_u8': (_i, [_p, _p, _p, _p, _d, _d, _p, _i, _i, _i, _p, _sz]),
+    'swem_png_capacity': (_sz, [_i, _i]),
+    'swem_png_workspace': (_sz, [_i, _i, _i]),
+    'swem_png_encode_u8': (_i, [_p, _p, _p, _p, _sz, _p, _i, _i, _i, _p, _sz]),
 }
 
 _lib = None

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libswem_hip.so')
 SOURCES = ['api.hip', 'conv.hip', 'bneck.hip', 'pointwise.hip', 'em.hip', 'match.hip', 'train.hip', 'train_conv.hip', 'metrics.hip',
-           'augment.hip', 'synth.hip', 'stage.hip']
+           'augment.hip', 'synth.hip', 'stage.hip', 'png.hip']
 # (source, extra flags, object): conv.hip a second time for conv_t256_kernel alone (-DSWEM_CONV_T256_ONLY: csrc/conv.hip)
 EXTRA_UNITS = [('conv.hip', ['-DSWEM_CONV_T256_ONLY'], 'conv_t256.o')]
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

@@ -11,6 +11,8 @@ utils/visualization.py:40-43).
   YouTube-VOS input size (YTVOS_Test.py:14-19, 75-91) are restated here; reading the files stays with the caller.
 * ``IndexMapWriter`` also maps indices to object ids (basic_evaluator.py:202-206) and writes the overlay pictures of
   VAL.VISUALIZE (utils/visualization.py:46-72, basic_evaluator.py:185-196, 241-265), both on the device.
+* ``IndexMapWriter(encode='device')`` encodes the palette PNGs on the device too (csrc/png.hip): the bytes
+  that cross to the host are the files' bytes, and the thread pool only writes them out.
 Nothing here touches the model.
 """
 import os
@@ -192,8 +194,22 @@ def default_palette(n=256):
     return pal.flatten().tolist()
 
 
+def png_capacity(H, W):
+    """swem_png_capacity (include/swem_hip_io.h): the largest PNG file `ops.png_encode_u8` writes for an H x W map -- every
+    segment stored, plus the headers.  0 for a shape the encoder refuses."""
+    from . import _lib
+    return int(_lib.query('swem_png_capacity', int(H), int(W)))
+
+
 class IndexMapWriter:
-    def __init__(self, out_dir, palette=None, workers=4, overlay_alpha=0.4):
+    def __init__(self, out_dir, palette=None, workers=4, overlay_alpha=0.4, encode='host'):
+        """encode='host': the index maps cross to the host as they are and PIL writes them on the thread pool.
+        encode='device': `ops.png_encode_u8` makes the files on the device; only their bytes cross, and
+        the pool writes them out unchanged.  The palette is then always written with 256 entries.  Overlay pictures are
+        PIL-encoded either way."""
+        if encode not in ('host', 'device'):
+            raise ValueError("IndexMapWriter: encode is 'host' or 'device', got %r" % (encode,))
+        self.encode = encode
         self.out_dir = out_dir
         self.palette = default_palette() if palette is None else palette
         self.overlay_alpha = overlay_alpha
@@ -209,7 +225,7 @@ class IndexMapWriter:
 
     def _to_host(self, tensors):
         """Asynchronous copies into pinned memory on the copy stream; (host tensors, event)."""
-        hosts = [torch.empty(t.shape, dtype=torch.uint8, pin_memory=True) for t in tensors]
+        hosts = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in tensors]
         ev = torch.cuda.Event()
         self.copy_stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.copy_stream):
@@ -240,25 +256,59 @@ class IndexMapWriter:
         stacked = torch.cat(preds, dim=0).contiguous()                 # (T-1,H,W) int64, device
         n = stacked.shape[0]
         u8 = ops.pack_u8(stacked) if id_table is None else ops.pack_u8_lut(stacked, id_table)
-        tensors, od = [u8], None
+        device = self.encode == 'device'
+        tensors, od = ([] if device else [u8]), None
         if overlay_frames_u8 is not None:
             od = os.path.join(self.out_dir, 'overlay', seq_name)
             os.makedirs(od, exist_ok=True)
             tensors.append(self._overlay(overlay_frames_u8[first_index:first_index + n], u8, u8.device))
-        hosts, ev = self._to_host(tensors)
         stems = [('%05d' % (first_index + t)) if names is None else names[first_index + t] for t in range(n)]
         kept = [keep is None or (stems[t] if names is not None else first_index + t) in keep for t in range(n)]
+        files = None
+        if device and any(kept):
+            files = self._encode([t for t in range(n) if kept[t]], u8)
+        hosts, ev = self._to_host(tensors)
 
         def write():
+            if files is not None:
+                for t, data in zip(files[0], self._files_to_host(*files[1:])):
+                    with open(os.path.join(d, stems[t] + '.png'), 'wb') as f:
+                        f.write(data)
             ev.synchronize()
-            arr = hosts[0].numpy()
             for t in range(n):
-                if kept[t]:
-                    save_seg_mask(arr[t], os.path.join(d, stems[t] + '.png'), self.palette)
+                if kept[t] and not device:
+                    save_seg_mask(hosts[0].numpy()[t], os.path.join(d, stems[t] + '.png'), self.palette)
                 if od is not None:
-                    save_rgb(hosts[1].numpy()[t], os.path.join(od, stems[t] + '.png'))
+                    save_rgb(hosts[-1].numpy()[t], os.path.join(od, stems[t] + '.png'))
             return sum(kept)
         self.pending.append(self.pool.submit(write))
+
+    def _encode(self, sel, u8):
+        """The frames `sel` of u8 (n,H,W) as PNG files on the device, and the copy of their offsets under way on the copy stream:
+        (sel, blob, offsets on the host, event).  Nothing here waits."""
+        if len(sel) == u8.shape[0]:
+            maps = u8
+        elif sel == list(range(sel[0], sel[-1] + 1)):
+            maps = u8[sel[0]:sel[-1] + 1]
+        else:
+            maps = torch.stack([u8[t] for t in sel])
+        blob, offsets = ops.png_encode_u8(maps, self._palette768())
+        (offs_host,), ev = self._to_host([offsets])
+        blob.record_stream(self.copy_stream)
+        return sel, blob, offs_host, ev
+
+    def _files_to_host(self, blob, offs_host, ev):
+        """Worker thread: wait for the offsets, copy blob[:total] on the copy stream -> the files' bytes."""
+        ev.synchronize()
+        offs = offs_host.tolist()
+        host = torch.empty(offs[-1], dtype=torch.uint8, pin_memory=True)
+        with torch.cuda.device(blob.device), torch.cuda.stream(self.copy_stream):
+            host.copy_(blob[:offs[-1]], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+        done.synchronize()
+        data = host.numpy()
+        return [data[offs[k]:offs[k + 1]].tobytes() for k in range(len(offs) - 1)]
 
     def save_first(self, seq_name, mask_onehot, id_table=None, name=None, overlay_frame_u8=None):
         """Frame 0's given annotation (basic_evaluator.py:180-187, 238-244); `id_table`, `name` and the (H,W,3) uint8
@@ -268,7 +318,12 @@ class IndexMapWriter:
         stem = '00000' if name is None else name
         idx, _ = ops.argmax_onehot(mask_onehot.float().contiguous(), want_onehot=False)
         u8 = ops.pack_u8(idx) if id_table is None else ops.pack_u8_lut(idx, id_table)
-        save_seg_mask(u8.cpu().numpy()[0], os.path.join(d, stem + '.png'), self.palette)
+        if self.encode == 'device':
+            blob, offsets = ops.png_encode_u8(u8, self._palette768())
+            with open(os.path.join(d, stem + '.png'), 'wb') as f:
+                f.write(blob[:int(offsets[-1])].cpu().numpy().tobytes())
+        else:
+            save_seg_mask(u8.cpu().numpy()[0], os.path.join(d, stem + '.png'), self.palette)
         if overlay_frame_u8 is not None:
             od = os.path.join(self.out_dir, 'overlay', seq_name)
             os.makedirs(od, exist_ok=True)
