@@ -33,6 +33,28 @@ extern "C" {
  *   59      int32: order of the frame-level ops  60..63  zero (swem_augment_static_u8 reads them: below)
  * An order is three 2-bit op codes, first op in bits 0-1: 0 brightness, 1 contrast, 2 saturation, 3 no op.
  * Label order: the 256 labels in the order of the clip's random priority (the inverse of the priority permutation). */
+enum { /* first word of each field of the frame record (words 60..63: swem_augment_static_u8, below) */
+  SWEM_AUG_M_AFF = 0,
+  SWEM_AUG_M_SRC = 6,
+  SWEM_AUG_TPS_AFFINE = 12,
+  SWEM_AUG_TPS_WX = 18,
+  SWEM_AUG_TPS_WY = 34,
+  SWEM_AUG_CLIP_FACTORS = 50,
+  SWEM_AUG_FRAME_FACTORS = 53,
+  SWEM_AUG_TPS_ON = 56,
+  SWEM_AUG_CLIP_ORDER = 57,
+  SWEM_AUG_GRAY = 58,
+  SWEM_AUG_FRAME_ORDER = 59,
+  SWEM_AUG_STATIC_FLAGS = 60,
+  SWEM_AUG_SRC_H = 61,
+  SWEM_AUG_SRC_W = 62,
+  SWEM_AUG_HUE = 63
+};
+enum { /* word SWEM_AUG_STATIC_FLAGS: bit 0, and the 2-bit field in bits 4-5 */
+  SWEM_AUG_FLAG_SRC_FILL = 1,
+  SWEM_AUG_FLAG_HUE_BEFORE_SHIFT = 4,
+  SWEM_AUG_FLAG_HUE_BEFORE_MASK = 3
+};
 enum { SWEM_AUG_REGION_IMAGE = 0, SWEM_AUG_REGION_FILL = 1, SWEM_AUG_REGION_OUTSIDE_TPS = 2 };
 
 /* Workspace of a call: [B][T][Ho][Wo] uint8 warped labels, [B][T][Ho][Wo] uint8 region codes, then (each 256-byte aligned)
@@ -84,6 +106,31 @@ int swem_augment_clips_u8(void *stream, const unsigned char *src, const unsigned
  *   rh = max(1, rint(sqrt(area hc wc / aspect))), rw = max(1, rint(sqrt(area hc wc aspect))),
  *   tx = lo + min(hi - lo, floor(ux (hi - lo + 1))) - rw/2,  lo = rw/2, hi = max(w0 - rw/2, rw/2)  (integer halves; y alike),
  *   present = 0 for k >= n_img and for an empty mask. */
+enum { /* clip record, frame record: first word of each field */
+  SWEM_SYNTH_N_IMG = 0,
+  SWEM_SYNTH_SIZES = 2,
+  SWEM_SYNTH_IDS = 16,
+  SWEM_SYNTH_PASTE = 0,
+  SWEM_SYNTH_OBJECTS = 8
+};
+enum { /* image statistics */
+  SWEM_SYNTH_STAT_NOT_HMIN = 0,
+  SWEM_SYNTH_STAT_NOT_WMIN = 1,
+  SWEM_SYNTH_STAT_HMAX1 = 2,
+  SWEM_SYNTH_STAT_WMAX1 = 3,
+  SWEM_SYNTH_STAT_COUNT = 4,
+  SWEM_SYNTH_STAT_SUM_R = 5,
+  SWEM_SYNTH_STAT_SUM_G = 6,
+  SWEM_SYNTH_STAT_SUM_B = 7
+};
+enum { /* placement */
+  SWEM_SYNTH_PLAN_RH = 0,
+  SWEM_SYNTH_PLAN_RW = 1,
+  SWEM_SYNTH_PLAN_TX = 2,
+  SWEM_SYNTH_PLAN_TY = 3,
+  SWEM_SYNTH_PLAN_ID = 4,
+  SWEM_SYNTH_PLAN_PRESENT = 5
+};
 
 /* Workspace of a call: the statistics, then (256-byte aligned) the placement table.  0 for non-positive sizes. */
 size_t swem_synth_workspace(int B, int T, int N);

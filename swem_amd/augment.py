@@ -6,11 +6,63 @@ The reference augments on CPU workers (datasets/video_dataset.py:139-192, 269-34
 uint8 frames and label maps into the four tensors of `SWEMTrainer.one_step`.  Parameters are plain data: a caller may hand in any
 transform, also ones `draw_params` never draws.
 """
+from types import SimpleNamespace
+
 import numpy as np
 
 IM_MEAN = (124, 116, 104)                  # data_utils.py:8, the affine's fill colour
-FRAME_WORDS, CLIP_WORDS = 64, 256          # include/swem_hip_data.h
-REGION_IMAGE, REGION_FILL, REGION_OUTSIDE_TPS = 0, 1, 2
+
+
+class Rec:
+    """The defines and enums of include/swem_hip_data.h without their SWEM_ prefix: record sizes, the first word of each field, the
+    flag bits of word STATIC_FLAGS, statistics and placement words (tests/test_abi.py holds the two lists equal)."""
+    AUG_MAX_CHANNELS, AUG_FRAME_WORDS, AUG_CLIP_WORDS = 8, 64, 256
+    AUG_M_AFF, AUG_M_SRC, AUG_TPS_AFFINE, AUG_TPS_WX, AUG_TPS_WY = 0, 6, 12, 18, 34
+    AUG_CLIP_FACTORS, AUG_FRAME_FACTORS, AUG_TPS_ON, AUG_CLIP_ORDER, AUG_GRAY, AUG_FRAME_ORDER = 50, 53, 56, 57, 58, 59
+    AUG_STATIC_FLAGS, AUG_SRC_H, AUG_SRC_W, AUG_HUE = 60, 61, 62, 63
+    AUG_FLAG_SRC_FILL, AUG_FLAG_HUE_BEFORE_SHIFT, AUG_FLAG_HUE_BEFORE_MASK = 1, 4, 3
+    AUG_REGION_IMAGE, AUG_REGION_FILL, AUG_REGION_OUTSIDE_TPS = 0, 1, 2
+    SYNTH_MAX_IMAGES, SYNTH_CLIP_WORDS, SYNTH_FRAME_WORDS, SYNTH_STAT_WORDS, SYNTH_PLAN_WORDS = 7, 32, 64, 8, 8
+    SYNTH_N_IMG, SYNTH_SIZES, SYNTH_IDS, SYNTH_PASTE, SYNTH_OBJECTS = 0, 2, 16, 0, 8
+    SYNTH_STAT_NOT_HMIN, SYNTH_STAT_NOT_WMIN, SYNTH_STAT_HMAX1, SYNTH_STAT_WMAX1 = 0, 1, 2, 3
+    SYNTH_STAT_COUNT, SYNTH_STAT_SUM_R, SYNTH_STAT_SUM_G, SYNTH_STAT_SUM_B = 4, 5, 6, 7
+    SYNTH_PLAN_RH, SYNTH_PLAN_RW, SYNTH_PLAN_TX, SYNTH_PLAN_TY, SYNTH_PLAN_ID, SYNTH_PLAN_PRESENT = 0, 1, 2, 3, 4, 5
+
+
+def frame_block_words(B, T):
+    """32-bit words of the parameter block of swem_augment_clips_u8 / swem_augment_static_u8: frame records, then label orders."""
+    return B * T * Rec.AUG_FRAME_WORDS + B * Rec.AUG_CLIP_WORDS
+
+
+def synth_block_words(B, T):
+    """32-bit words of the parameter block of swem_synth_frames_u8: clip records, then frame records."""
+    return B * Rec.SYNTH_CLIP_WORDS + B * T * Rec.SYNTH_FRAME_WORDS
+
+
+def _align256(n):
+    return (n + 255) // 256 * 256
+
+
+def augment_layout(B, T, Ho, Wo):
+    """Byte offsets of the workspace of swem_augment_clips_u8 (aug_layout of csrc/augment.hip): warped labels, region codes,
+    presence bits, gray partial sums (one per 32x8 tile), total = swem_augment_workspace."""
+    px = B * T * Ho * Wo
+    tiles = -(-Wo // 32) * -(-Ho // 8)
+    lay = {'wlab': 0, 'wreg': px, 'presence': _align256(2 * px)}
+    lay['partial'] = lay['presence'] + _align256(B * 8 * 4)
+    lay['total'] = lay['partial'] + _align256(B * T * tiles * 4)
+    return lay
+
+
+def synth_layout(B, T, N):
+    """Byte offsets of the workspace of swem_synth_frames_u8 (synth_layout of csrc/synth.hip): statistics, placement table,
+    total = swem_synth_workspace."""
+    lay = {'stats': 0, 'plan': _align256(B * N * Rec.SYNTH_STAT_WORDS * 4)}
+    lay['total'] = lay['plan'] + _align256(B * T * N * Rec.SYNTH_PLAN_WORDS * 4)
+    return lay
+
+
+REGION_IMAGE, REGION_FILL, REGION_OUTSIDE_TPS = Rec.AUG_REGION_IMAGE, Rec.AUG_REGION_FILL, Rec.AUG_REGION_OUTSIDE_TPS
 BRIGHTNESS, CONTRAST, SATURATION, NO_OP = 0, 1, 2, 3
 TPS_GRID = 4
 # the 16 fixed anchors X_k, k = 4*row + column, (x, y) on [-1,1]^2 (thinplatespline/utils.py:13-22)
@@ -166,30 +218,57 @@ def pack_params(clips):
     """The parameter block of a call (include/swem_hip_data.h) for a list of clip dicts as `draw_params` returns them: an int32
     array of B*T*64 + B*256 words, the fp32 fields bit-cast.  All the maths before the cast to fp32 is float64."""
     B, T = len(clips), len(clips[0]['frames'])
-    block = np.zeros(B * T * FRAME_WORDS + B * CLIP_WORDS, np.int32)
-    fl = block.view(np.float32)
+    block = np.zeros(frame_block_words(B, T), np.int32)
+    frames = block[:B * T * Rec.AUG_FRAME_WORDS].reshape(B, T, Rec.AUG_FRAME_WORDS)
+    orders = block[B * T * Rec.AUG_FRAME_WORDS:].reshape(B, Rec.AUG_CLIP_WORDS)
     for b, clip in enumerate(clips):
         if len(clip['frames']) != T or tuple(clip['out_hw']) != tuple(clips[0]['out_hw']):
             raise ValueError('the clips of one call share T and the output size')
         for t, fr in enumerate(clip['frames']):
-            o = (b * T + t) * FRAME_WORDS
+            rec = frames[b, t]
+            fl = rec.view(np.float32)
             M_aff, M_src = frame_matrices(clip, fr)
-            fl[o:o + 6] = centred(M_aff, clip['out_hw']).reshape(-1)
-            fl[o + 6:o + 12] = centred(M_src, clip['out_hw']).reshape(-1)
+            fl[Rec.AUG_M_AFF:Rec.AUG_M_AFF + 6] = centred(M_aff, clip['out_hw']).reshape(-1)
+            fl[Rec.AUG_M_SRC:Rec.AUG_M_SRC + 6] = centred(M_src, clip['out_hw']).reshape(-1)
             if fr.get('tps_on', False):
                 A, W = tps_coefficients(fr['tps_Y'])
-                fl[o + 12:o + 18] = A.T.reshape(-1)
-                fl[o + 18:o + 34] = W[:, 0]
-                fl[o + 34:o + 50] = W[:, 1]
-                block[o + 56] = 1
-            fl[o + 50:o + 53] = clip.get('factors', (1.0, 1.0, 1.0))
-            fl[o + 53:o + 56] = fr.get('factors', (1.0, 1.0, 1.0))
-            block[o + 57] = order_code(clip.get('order', (NO_OP,) * 3))
-            block[o + 58] = int(bool(clip.get('gray', False)))
-            block[o + 59] = order_code(fr.get('order', (NO_OP,) * 3))
-        o = B * T * FRAME_WORDS + b * CLIP_WORDS
-        block[o:o + CLIP_WORDS] = label_order(clip.get('prio', np.arange(256)))
+                fl[Rec.AUG_TPS_AFFINE:Rec.AUG_TPS_AFFINE + 6] = A.T.reshape(-1)
+                fl[Rec.AUG_TPS_WX:Rec.AUG_TPS_WX + 16] = W[:, 0]
+                fl[Rec.AUG_TPS_WY:Rec.AUG_TPS_WY + 16] = W[:, 1]
+                rec[Rec.AUG_TPS_ON] = 1
+            fl[Rec.AUG_CLIP_FACTORS:Rec.AUG_CLIP_FACTORS + 3] = clip.get('factors', (1.0, 1.0, 1.0))
+            fl[Rec.AUG_FRAME_FACTORS:Rec.AUG_FRAME_FACTORS + 3] = fr.get('factors', (1.0, 1.0, 1.0))
+            rec[Rec.AUG_CLIP_ORDER] = order_code(clip.get('order', (NO_OP,) * 3))
+            rec[Rec.AUG_GRAY] = int(bool(clip.get('gray', False)))
+            rec[Rec.AUG_FRAME_ORDER] = order_code(fr.get('order', (NO_OP,) * 3))
+        orders[b] = label_order(clip.get('prio', np.arange(256)))
     return block
+
+
+class StagedBlock:
+    """A parameter block of `words` 32-bit words on the device, refilled through pinned memory: `dev`, `pinned` (int32 tensors) and
+    `done`, the event behind the last copy out of a pinned block.  Blocks that are refilled together share one event (`done=`):
+    all but the last are filled with record=False, so that every copy stands in front of the one event the next refill waits on."""
+
+    def __init__(self, words, device, done=None):
+        import torch
+        self.device = device
+        self.dev = torch.zeros(words, dtype=torch.int32, device=device)
+        self.pinned = torch.zeros(words, dtype=torch.int32).pin_memory()
+        self.done = torch.cuda.Event() if done is None else done
+
+    def fill(self, block, what='a block', record=True):
+        """Copy a numpy block of 32-bit words to the device without blocking; returns the device tensor."""
+        import torch
+        if block.dtype.itemsize != 4 or block.size != self.pinned.numel():
+            raise ValueError('%s has %d 32-bit words, got %d' % (what, self.pinned.numel(), block.size))
+        self.done.synchronize()          # (the previous copy out of the pinned block, not the kernels)
+        self.pinned.numpy()[:] = block.view(np.int32)
+        with torch.cuda.device(self.device):
+            self.dev.copy_(self.pinned, non_blocking=True)
+            if record:
+                self.done.record()
+        return self.dev
 
 
 class ClipAugmenter:
@@ -209,7 +288,7 @@ class ClipAugmenter:
         self.out_hw = (int(out_hw[0]), int(out_hw[1]))
         self.N, self.T = int(max_nobj), int(T)
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        self._state = {}      # B -> (workspace, device block, pinned block, copy-done event)
+        self._state = {}      # B -> (workspace, StagedBlock of the frame records and label orders)
 
     def _buffers(self, B):
         import torch
@@ -220,28 +299,17 @@ class ClipAugmenter:
             nbytes = _lib.query('swem_augment_workspace', B, self.T, Ho, Wo)
             if nbytes == 0:
                 raise _lib.SwemHipError('ClipAugmenter: no workspace for B=%d T=%d %dx%d' % (B, self.T, Ho, Wo))
-            words = B * self.T * FRAME_WORDS + B * CLIP_WORDS
-            st = (torch.empty(nbytes, dtype=torch.uint8, device=self.device),
-                  torch.zeros(words, dtype=torch.int32, device=self.device),
-                  torch.zeros(words, dtype=torch.int32).pin_memory(), torch.cuda.Event())
+            st = SimpleNamespace(ws=torch.empty(nbytes, dtype=torch.uint8, device=self.device),
+                                 params=StagedBlock(frame_block_words(B, self.T), self.device))
             self._state[B] = st
         return st
 
     def set_params(self, params, B=None):
         """Copy a parameter block (or pack a list of clip dicts) into the static device buffer of its batch size."""
-        import torch
         block = params if isinstance(params, np.ndarray) else pack_params(params)
         if B is None:
-            B = block.size // (self.T * FRAME_WORDS + CLIP_WORDS)
-        _ws, dev, pinned, done = self._buffers(B)
-        if block.dtype.itemsize != 4 or block.size != pinned.numel():
-            raise ValueError('a block of B=%d, T=%d has %d 32-bit words, got %d' % (B, self.T, pinned.numel(), block.size))
-        done.synchronize()          # (the previous copy out of the pinned block, not the kernels)
-        pinned.numpy()[:] = block.view(np.int32)
-        with torch.cuda.device(self.device):
-            dev.copy_(pinned, non_blocking=True)
-            done.record()
-        return dev
+            B = block.size // frame_block_words(1, self.T)
+        return self._buffers(B).params.fill(block, 'a block of B=%d, T=%d' % (B, self.T))
 
     def empty_out(self, B):
         import torch
@@ -259,36 +327,34 @@ class ClipAugmenter:
             raise ValueError('ClipAugmenter was made for T=%d frames, got %d' % (self.T, labels_u8.shape[1]))
         if params is not None:
             self.set_params(params, B)
-        ws, dev, _pinned, _done = self._buffers(B)
+        st = self._buffers(B)
         if out is None:
             out = self.empty_out(B)
         with torch.cuda.device(self.device):
-            ops.augment_clips(frames_u8, labels_u8, dev, out[0], out[1], out[2], out[3], out[4], ws, b0)
+            ops.augment_clips(frames_u8, labels_u8, st.params.dev, out[0], out[1], out[2], out[3], out[4], st.ws, b0)
         return out
 
     # ---- what the last call of batch size B left in the workspace (views, for checks)
-    def _px(self, B):
-        return B * self.T * self.out_hw[0] * self.out_hw[1]
+    def _ws_bytes(self, B, field, nbytes):
+        o = augment_layout(B, self.T, *self.out_hw)[field]
+        return self._buffers(B).ws[o:o + nbytes]
 
     def warped_labels(self, B):
-        return self._buffers(B)[0][:self._px(B)].view(B, self.T, *self.out_hw)
+        return self._ws_bytes(B, 'wlab', B * self.T * self.out_hw[0] * self.out_hw[1]).view(B, self.T, *self.out_hw)
 
     def regions(self, B):
-        return self._buffers(B)[0][self._px(B):2 * self._px(B)].view(B, self.T, *self.out_hw)
+        return self._ws_bytes(B, 'wreg', B * self.T * self.out_hw[0] * self.out_hw[1]).view(B, self.T, *self.out_hw)
 
     def presence(self, B):
         """(B, 256) bool: the labels of the warped frame 0 (0 and 255 are never entered)."""
         import torch
-        o = (2 * self._px(B) + 255) // 256 * 256
-        words = self._buffers(B)[0][o:o + B * 32].view(torch.int32).view(B, 8)
+        words = self._ws_bytes(B, 'presence', B * 32).view(torch.int32).view(B, 8)
         return ((words[:, :, None] >> torch.arange(32, device=words.device)) & 1).bool().view(B, 256)
 
 
 # ------------------------------------------------------------------------------------ stage 0: clips from static images
 # (datasets/static_dataset.py; csrc/synth.hip and the static form of csrc/augment.hip; DESIGN.md section 9)
-SYNTH_CLIP_WORDS, SYNTH_FRAME_WORDS, SYNTH_STAT_WORDS, SYNTH_PLAN_WORDS, SYNTH_MAX_IMAGES = 32, 64, 8, 8, 7
 HUE = 3                                    # the fourth op of the clip-level jitter's drawn order
-FLAG_SRC_FILL = 1                          # word 60, bit 0: outside the source is FILL
 
 
 def static_scale(size0, out_hw):
@@ -307,8 +373,8 @@ def draw_static_params(rng, T, sizes, out_hw):
     in random order; TPS (p = 1) with noise (U - 0.5) * 0.3 on the four inner anchors."""
     sizes = [(int(h), int(w)) for h, w in sizes]
     n_img = len(sizes)
-    if not 1 <= n_img <= SYNTH_MAX_IMAGES:
-        raise ValueError('a static clip has 1..%d images, got %d' % (SYNTH_MAX_IMAGES, n_img))
+    if not 1 <= n_img <= Rec.SYNTH_MAX_IMAGES:
+        raise ValueError('a static clip has 1..%d images, got %d' % (Rec.SYNTH_MAX_IMAGES, n_img))
     Ho, Wo = out_hw
     h0, w0 = sizes[0]
     r = static_scale(sizes[0], out_hw)
@@ -382,35 +448,34 @@ def pack_static_params(clips, max_images=None):
             frames.append(dict(fr, M_aff=M_aff, M_src=M_src))
         full.append(dict(clip, frames=frames))
     block = pack_params(full)
-    fl = block.view(np.float32)
-    synth = np.zeros(B * SYNTH_CLIP_WORDS + B * T * SYNTH_FRAME_WORDS, np.int32)
-    sfl = synth.view(np.float32)
+    frames = block[:B * T * Rec.AUG_FRAME_WORDS].reshape(B, T, Rec.AUG_FRAME_WORDS)
+    synth = np.zeros(synth_block_words(B, T), np.int32)
+    sclips = synth[:B * Rec.SYNTH_CLIP_WORDS].reshape(B, Rec.SYNTH_CLIP_WORDS)
+    sframes = synth[B * Rec.SYNTH_CLIP_WORDS:].reshape(B, T, Rec.SYNTH_FRAME_WORDS)
     for b, clip in enumerate(clips):
         sizes = clip['sizes']
         n_img = len(sizes)
-        if not 1 <= n_img <= (SYNTH_MAX_IMAGES if max_images is None else max_images):
+        if not 1 <= n_img <= (Rec.SYNTH_MAX_IMAGES if max_images is None else max_images):
             raise ValueError('clip %d has %d images' % (b, n_img))
         before = int(clip.get('hue_before', 0))
-        if not 0 <= before <= 3:
+        if not 0 <= before <= Rec.AUG_FLAG_HUE_BEFORE_MASK:
             raise ValueError('hue_before counts the clip-level ops in front of the hue op: 0..3')
-        o = b * SYNTH_CLIP_WORDS
-        synth[o] = n_img
-        ids = clip.get('ids', list(range(1, n_img + 1)))
-        for k, (h, w) in enumerate(sizes):
-            synth[o + 2 + 2 * k], synth[o + 3 + 2 * k] = int(h), int(w)
-            synth[o + 16 + k] = int(ids[k])
+        sclips[b, Rec.SYNTH_N_IMG] = n_img
+        sclips[b, Rec.SYNTH_SIZES:Rec.SYNTH_SIZES + 2 * n_img] = np.asarray(sizes, np.int64).reshape(-1)
+        sclips[b, Rec.SYNTH_IDS:Rec.SYNTH_IDS + n_img] = clip.get('ids', list(range(1, n_img + 1)))[:n_img]
         for t, fr in enumerate(clip['frames']):
-            o = (b * T + t) * FRAME_WORDS
-            block[o + 60] = (FLAG_SRC_FILL if clip.get('src_fill', True) else 0) | (before << 4)
-            block[o + 61], block[o + 62] = int(sizes[0][0]), int(sizes[0][1])
-            fl[o + 63] = clip.get('hue', 0.0)
-            o = B * SYNTH_CLIP_WORDS + (b * T + t) * SYNTH_FRAME_WORDS
+            rec = frames[b, t]
+            rec[Rec.AUG_STATIC_FLAGS] = (Rec.AUG_FLAG_SRC_FILL if clip.get('src_fill', True) else 0) | \
+                (before << Rec.AUG_FLAG_HUE_BEFORE_SHIFT)
+            rec[Rec.AUG_SRC_H], rec[Rec.AUG_SRC_W] = int(sizes[0][0]), int(sizes[0][1])
+            rec.view(np.float32)[Rec.AUG_HUE] = clip.get('hue', 0.0)
+            srec = sframes[b, t]
             paste = fr.get('paste', list(range(n_img)))
-            synth[o:o + len(paste)] = paste
-            synth[o + len(paste):o + SYNTH_MAX_IMAGES] = -1
+            srec[Rec.SYNTH_PASTE:Rec.SYNTH_PASTE + len(paste)] = paste
+            srec[Rec.SYNTH_PASTE + len(paste):Rec.SYNTH_PASTE + Rec.SYNTH_MAX_IMAGES] = -1
             if n_img > 1 or 'objects' in fr:
                 obj = np.asarray(fr['objects'], np.float32).reshape(n_img, 4)
-                sfl[o + 8:o + 8 + 4 * n_img] = obj.reshape(-1)
+                srec.view(np.float32)[Rec.SYNTH_OBJECTS:Rec.SYNTH_OBJECTS + 4 * n_img] = obj.reshape(-1)
     return synth, block
 
 
@@ -428,9 +493,9 @@ class StaticClipSynthesizer(ClipAugmenter):
     def __init__(self, out_hw, max_nobj, T, slot_hw, device=None):
         super().__init__(out_hw, max_nobj, T, device)
         self.slot_hw = (int(slot_hw[0]), int(slot_hw[1]))
-        if not 1 <= self.N <= SYNTH_MAX_IMAGES:
-            raise ValueError('StaticClipSynthesizer: 1 <= max_nobj <= %d, got %d' % (SYNTH_MAX_IMAGES, self.N))
-        self._synth = {}      # B -> (workspace, device block, pinned block, comp, comp_lab)
+        if not 1 <= self.N <= Rec.SYNTH_MAX_IMAGES:
+            raise ValueError('StaticClipSynthesizer: 1 <= max_nobj <= %d, got %d' % (Rec.SYNTH_MAX_IMAGES, self.N))
+        self._synth = {}      # B -> (workspace, StagedBlock of the synth records, comp, comp_lab)
 
     def _synth_buffers(self, B):
         import torch
@@ -440,29 +505,21 @@ class StaticClipSynthesizer(ClipAugmenter):
             nbytes = _lib.query('swem_synth_workspace', B, self.T, self.N)
             if nbytes == 0:
                 raise _lib.SwemHipError('StaticClipSynthesizer: no workspace for B=%d T=%d N=%d' % (B, self.T, self.N))
-            words = B * SYNTH_CLIP_WORDS + B * self.T * SYNTH_FRAME_WORDS
             Hm, Wm = self.slot_hw
-            st = (torch.zeros(nbytes, dtype=torch.uint8, device=self.device),
-                  torch.zeros(words, dtype=torch.int32, device=self.device), torch.zeros(words, dtype=torch.int32).pin_memory(),
-                  torch.zeros((B, self.T, Hm, Wm, 3), dtype=torch.uint8, device=self.device),
-                  torch.zeros((B, self.T, Hm, Wm), dtype=torch.uint8, device=self.device))
+            st = SimpleNamespace(ws=torch.zeros(nbytes, dtype=torch.uint8, device=self.device),
+                                 params=StagedBlock(synth_block_words(B, self.T), self.device, done=self._buffers(B).params.done),
+                                 comp=torch.zeros((B, self.T, Hm, Wm, 3), dtype=torch.uint8, device=self.device),
+                                 comp_lab=torch.zeros((B, self.T, Hm, Wm), dtype=torch.uint8, device=self.device))
             self._synth[B] = st
         return st
 
     def set_params(self, params, B=None):
         """Copy a pair of packed blocks (or pack a list of clip dicts) into the static device buffers of its batch size."""
-        import torch
         synth, block = params if isinstance(params, tuple) else pack_static_params(params, self.N)
         if B is None:
-            B = block.size // (self.T * FRAME_WORDS + CLIP_WORDS)
-        _ws, sdev, spinned, _c, _l = self._synth_buffers(B)
-        if synth.dtype.itemsize != 4 or synth.size != spinned.numel():
-            raise ValueError('a synth block of B=%d, T=%d has %d 32-bit words, got %d' % (B, self.T, spinned.numel(), synth.size))
-        self._buffers(B)[3].synchronize()
-        spinned.numpy()[:] = synth.view(np.int32)
-        with torch.cuda.device(self.device):
-            sdev.copy_(spinned, non_blocking=True)
-        return super().set_params(block, B)          # (records the event behind both copies)
+            B = block.size // frame_block_words(1, self.T)
+        self._synth_buffers(B).params.fill(synth, 'a synth block of B=%d, T=%d' % (B, self.T), record=False)
+        return super().set_params(block, B)          # (records the shared event behind both copies)
 
     def __call__(self, imgs_u8, masks_u8, params=None, out=None, b0=0):
         import torch
@@ -473,14 +530,10 @@ class StaticClipSynthesizer(ClipAugmenter):
                              % ((self.N,) + self.slot_hw + (tuple(masks_u8.shape),)))
         if params is not None:
             self.set_params(params, B)
-        ws, dev, _pinned, _done = self._buffers(B)
-        sws, sdev, _sp, comp, comp_lab = self._synth_buffers(B)
-        if out is None:
-            out = self.empty_out(B)
+        syn = self._synth_buffers(B)
         with torch.cuda.device(self.device):
-            ops.synth_frames(imgs_u8, masks_u8, sdev, comp, comp_lab, sws)
-            ops.augment_static(comp, comp_lab, dev, out[0], out[1], out[2], out[3], out[4], ws, b0)
-        return out
+            ops.synth_frames(imgs_u8, masks_u8, syn.params.dev, syn.comp, syn.comp_lab, syn.ws)
+        return self.warp(syn.comp, syn.comp_lab, None, out, b0)
 
     def warp(self, comp, comp_lab, params=None, out=None, b0=0):
         """The second stage alone on given composites (B,T,Hmax,Wmax,3) / (B,T,Hmax,Wmax): the static chain of the parameters."""
@@ -489,29 +542,32 @@ class StaticClipSynthesizer(ClipAugmenter):
         B = comp_lab.shape[0]
         if params is not None:
             self.set_params(params, B)
-        ws, dev, _pinned, _done = self._buffers(B)
+        st = self._buffers(B)
         if out is None:
             out = self.empty_out(B)
         with torch.cuda.device(self.device):
-            ops.augment_static(comp, comp_lab, dev, out[0], out[1], out[2], out[3], out[4], ws, b0)
+            ops.augment_static(comp, comp_lab, st.params.dev, out[0], out[1], out[2], out[3], out[4], st.ws, b0)
         return out
 
     # ---- what the last call of batch size B left behind (views / small copies, for checks)
     def composites(self, B):
-        return self._synth_buffers(B)[3], self._synth_buffers(B)[4]
+        return self._synth_buffers(B).comp, self._synth_buffers(B).comp_lab
+
+    def _synth_words(self, B, field, shape):
+        import torch
+        o = synth_layout(B, self.T, self.N)[field]
+        return self._synth_buffers(B).ws[o:o + 4 * int(np.prod(shape))].view(torch.int32).view(*shape)
 
     def stats(self, B):
         """(B, N, 8) int64: hmin, wmin, hmax + 1, wmax + 1, count, sum r, sum g, sum b of every image's foreground (the box of
         an empty mask is meaningless: count 0)."""
         import torch
-        raw = self._synth_buffers(B)[0][:B * self.N * SYNTH_STAT_WORDS * 4].view(torch.int32).view(B, self.N, SYNTH_STAT_WORDS)
+        raw = self._synth_words(B, 'stats', (B, self.N, Rec.SYNTH_STAT_WORDS))
         st = raw.to(torch.int64) & 0xffffffff
-        st[:, :, :2] = (~raw[:, :, :2]).to(torch.int64) & 0xffffffff
+        for w in (Rec.SYNTH_STAT_NOT_HMIN, Rec.SYNTH_STAT_NOT_WMIN):
+            st[:, :, w] = (~raw[:, :, w]).to(torch.int64) & 0xffffffff
         return st
 
     def plan(self, B):
         """(B, T, N, 6) int32: rh, rw, tx, ty, id, present of every (frame, object)."""
-        import torch
-        o = (B * self.N * SYNTH_STAT_WORDS * 4 + 255) // 256 * 256
-        n = B * self.T * self.N * SYNTH_PLAN_WORDS
-        return self._synth_buffers(B)[0][o:o + 4 * n].view(torch.int32).view(B, self.T, self.N, SYNTH_PLAN_WORDS)[..., :6]
+        return self._synth_words(B, 'plan', (B, self.T, self.N, Rec.SYNTH_PLAN_WORDS))[..., :Rec.SYNTH_PLAN_PRESENT + 1]

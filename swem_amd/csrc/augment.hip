@@ -9,6 +9,7 @@
 //                      (every block repeats the clip's 256-entry scan: a ballot and a prefix count), masks, label, valid, found.
 // No float atomics: two runs give the same bits.
 #include "common.h"
+#include "image_sample.h"
 #include "../../include/swem_hip_data.h"
 
 // Both forms of the two kernels (the clips' and the static chain's) must give the same bits where their parameters agree.  hipcc's
@@ -37,10 +38,6 @@ inline AugLayout aug_layout(int B, int T, int Ho, int Wo) {
   l.total = l.partial + align_up((size_t)B * T * l.tiles * sizeof(float), 256);
   return l;
 }
-
-// the project's cubic (pointwise.hip, ATen's upsample_bicubic2d: A = -0.75)
-__device__ __forceinline__ float aug_cubic1(float x) { return (1.25f * x - 2.25f) * x * x + 1.f; }
-__device__ __forceinline__ float aug_cubic2(float x) { return ((-0.75f * x + 3.75f) * x - 6.f) * x + 3.f; }
 
 __device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
 __device__ __forceinline__ float gray_of(float r, float g, float b) { return 0.299f * r + 0.587f * g + 0.114f * b; }
@@ -89,12 +86,7 @@ __device__ __forceinline__ float block_sum(float v, float *red) {
   return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-__global__ __launch_bounds__(256) void aug_clear_kernel(unsigned *__restrict__ words, int n) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) words[i] = 0u;
-}
-
-// STATIC: the static chain's form (swem_augment_static_u8), which reads words 60..63 of the frame record
+// STATIC: the static chain's form (swem_augment_static_u8), which reads the frame record's last four words
 template <bool STATIC>
 __global__ __launch_bounds__(256) void aug_warp_kernel(const unsigned char *__restrict__ src, const unsigned char *__restrict__ lab,
                                                        const float *__restrict__ params, float *__restrict__ frames,
@@ -113,9 +105,9 @@ __global__ __launch_bounds__(256) void aug_warp_kernel(const unsigned char *__re
   int hs = Hs, ws = Ws;
   bool src_fill = false;
   if constexpr (STATIC) {
-    if (PI[61] >= 1 && PI[61] <= Hs) hs = PI[61];
-    if (PI[62] >= 1 && PI[62] <= Ws) ws = PI[62];
-    src_fill = (PI[60] & 1) != 0;
+    if (PI[SWEM_AUG_SRC_H] >= 1 && PI[SWEM_AUG_SRC_H] <= Hs) hs = PI[SWEM_AUG_SRC_H];
+    if (PI[SWEM_AUG_SRC_W] >= 1 && PI[SWEM_AUG_SRC_W] <= Ws) ws = PI[SWEM_AUG_SRC_W];
+    src_fill = (PI[SWEM_AUG_STATIC_FLAGS] & SWEM_AUG_FLAG_SRC_FILL) != 0;
   }
 
   const int i = (tile % tiles_x) * AUG_TW + (threadIdx.x & (AUG_TW - 1));
@@ -125,17 +117,18 @@ __global__ __launch_bounds__(256) void aug_warp_kernel(const unsigned char *__re
   if (active) {
     // 1. thin-plate spline (thinplatespline/batch.py:115-133: a linspace grid, read back as grid_sample, align_corners=False)
     float u = (float)i, v = (float)j;
-    if (PI[56]) {
+    if (PI[SWEM_AUG_TPS_ON]) {
+      const float *Q = P + SWEM_AUG_TPS_AFFINE, *WX = P + SWEM_AUG_TPS_WX, *WY = P + SWEM_AUG_TPS_WY;
       const float xn = -1.f + (2.f * (float)i) / (float)(Wo - 1), yn = -1.f + (2.f * (float)j) / (float)(Ho - 1);
-      float qx = P[12] + P[13] * xn + P[14] * yn, qy = P[15] + P[16] * xn + P[17] * yn;
+      float qx = Q[0] + Q[1] * xn + Q[2] * yn, qy = Q[3] + Q[4] * xn + Q[5] * yn;
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
         const float ax = (float)(-1.0 + 2.0 * (k & 3) / 3.0), ay = (float)(-1.0 + 2.0 * (k >> 2) / 3.0);
         const float dx = xn - ax, dy = yn - ay;
         const float d = dx * dx + dy * dy;
         const float U = d * logf(d + 1e-9f);
-        qx += P[18 + k] * U;
-        qy += P[34 + k] * U;
+        qx += WX[k] * U;
+        qy += WY[k] * U;
       }
       u = ((qx + 1.f) * (float)Wo - 1.f) * 0.5f;
       v = ((qy + 1.f) * (float)Ho - 1.f) * 0.5f;
@@ -143,9 +136,10 @@ __global__ __launch_bounds__(256) void aug_warp_kernel(const unsigned char *__re
     const bool outside = u <= -1.f || u >= (float)Wo || v <= -1.f || v >= (float)Ho;
     // 2. affine, 3. crop and flip: two affine forms of the centred coordinate
     const float xc = u + 0.5f - 0.5f * (float)Wo, yc = v + 0.5f - 0.5f * (float)Ho;
-    const float xa = P[0] * xc + P[1] * yc + P[2], ya = P[3] * xc + P[4] * yc + P[5];
+    const float *MA = P + SWEM_AUG_M_AFF, *MS = P + SWEM_AUG_M_SRC;
+    const float xa = MA[0] * xc + MA[1] * yc + MA[2], ya = MA[3] * xc + MA[4] * yc + MA[5];
     bool fill = xa < 0.f || xa >= (float)Wo || ya < 0.f || ya >= (float)Ho;
-    const float sx = P[6] * xc + P[7] * yc + P[8], sy = P[9] * xc + P[10] * yc + P[11];
+    const float sx = MS[0] * xc + MS[1] * yc + MS[2], sy = MS[3] * xc + MS[4] * yc + MS[5];
     if constexpr (STATIC) fill = fill || (src_fill && (sx < 0.f || sx >= (float)ws || sy < 0.f || sy >= (float)hs));
     // 4. sample
     float r = 0.f, g = 0.f, bl = 0.f;
@@ -164,31 +158,14 @@ __global__ __launch_bounds__(256) void aug_warp_kernel(const unsigned char *__re
       const unsigned char *S = src + frame_px * 3;
       const float bx = sx - 0.5f, by = sy - 0.5f;
       const float fx = floorf(bx), fy = floorf(by);
-      const int ix = (int)fx, iy = (int)fy;
-      const float tx = bx - fx, ty = by - fy;
-      const float wx[4] = {aug_cubic2(tx + 1.f), aug_cubic1(tx), aug_cubic1(1.f - tx), aug_cubic2(2.f - tx)};
-      const float wy[4] = {aug_cubic2(ty + 1.f), aug_cubic1(ty), aug_cubic1(1.f - ty), aug_cubic2(2.f - ty)};
-      int xo[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) xo[q] = 3 * min(max(ix - 1 + q, 0), ws - 1);
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const unsigned char *row = S + (size_t)min(max(iy - 1 + a, 0), hs - 1) * Ws * 3;
-        float rr = 0.f, rg = 0.f, rb = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const unsigned char *p = row + xo[q];
-          rr += wx[q] * (float)p[0];
-          rg += wx[q] * (float)p[1];
-          rb += wx[q] * (float)p[2];
-        }
-        r += wy[a] * rr;
-        g += wy[a] * rg;
-        bl += wy[a] * rb;
-      }
-      r /= 255.f;
-      g /= 255.f;
-      bl /= 255.f;
+      float wx[4], wy[4], acc[3];
+      cubic_weights(bx - fx, wx);
+      cubic_weights(by - fy, wy);
+      cubic_accumulate<3, 0>((int)fx, (int)fy, ws, hs, wx, wy,
+                          [&](int yy, int xx, float tap[3]) { rgb_bytes(S + (size_t)yy * Ws * 3 + 3 * xx, tap); }, acc);
+      r = acc[0] / 255.f;
+      g = acc[1] / 255.f;
+      bl = acc[2] / 255.f;
     }
     const size_t plane = (size_t)Ho * Wo, pix = (size_t)j * Wo + i;
     float *F = frames + bt * 3 * plane + pix;
@@ -265,18 +242,18 @@ __global__ __launch_bounds__(256) void aug_finish_kernel(const float *__restrict
   float r = F[0], g = F[plane], bl = F[2 * plane];
   if (region == SWEM_AUG_REGION_IMAGE) {   // (the fill enters after the clip-level ops)
     bool hue = false;
-    if constexpr (STATIC) hue = P[63] != 0.f;
+    if constexpr (STATIC) hue = P[SWEM_AUG_HUE] != 0.f;
     if (hue) {   // the clip-level jitter's four ops: `before` of the three, the hue op, the rest
-      const int before = (PI[60] >> 4) & 3;
-      jitter(r, g, bl, PI[57] | (0x3f << (2 * before)), P + 50, mean);
-      hue_shift(r, g, bl, P[63]);
-      jitter(r, g, bl, PI[57] | ((1 << (2 * before)) - 1), P + 50, mean);
+      const int before = (PI[SWEM_AUG_STATIC_FLAGS] >> SWEM_AUG_FLAG_HUE_BEFORE_SHIFT) & SWEM_AUG_FLAG_HUE_BEFORE_MASK;
+      jitter(r, g, bl, PI[SWEM_AUG_CLIP_ORDER] | (0x3f << (2 * before)), P + SWEM_AUG_CLIP_FACTORS, mean);
+      hue_shift(r, g, bl, P[SWEM_AUG_HUE]);
+      jitter(r, g, bl, PI[SWEM_AUG_CLIP_ORDER] | ((1 << (2 * before)) - 1), P + SWEM_AUG_CLIP_FACTORS, mean);
     } else {
-      jitter(r, g, bl, PI[57], P + 50, mean);
+      jitter(r, g, bl, PI[SWEM_AUG_CLIP_ORDER], P + SWEM_AUG_CLIP_FACTORS, mean);
     }
-    if (PI[58]) r = g = bl = gray_of(r, g, bl);
+    if (PI[SWEM_AUG_GRAY]) r = g = bl = gray_of(r, g, bl);
   }
-  jitter(r, g, bl, PI[59], P + 53, mean);
+  jitter(r, g, bl, PI[SWEM_AUG_FRAME_ORDER], P + SWEM_AUG_FRAME_FACTORS, mean);
   F[0] = r;
   F[plane] = g;
   F[2 * plane] = bl;
@@ -316,7 +293,7 @@ int augment_launch(const char *who, void *stream, const unsigned char *src, cons
   if constexpr (STATIC) {
     // a launch, not a memset node: replayed back to back, a captured call's memset node was seen to leave a stale pattern in
     // the presence set; the clips' entry keeps its memset node, as it always had
-    hipLaunchKernelGGL(aug_clear_kernel, dim3((unsigned)cdiv((long long)B * 8, 256)), dim3(256), 0, ST, presence, B * 8);
+    hipLaunchKernelGGL(clear_words_kernel, dim3((unsigned)cdiv((long long)B * 8, 256)), dim3(256), 0, ST, presence, B * 8);
     SWEM_CHECK_LAUNCH("aug_clear");
   } else {
     hipError_t e = hipMemsetAsync(presence, 0, (size_t)B * 8 * sizeof(unsigned), ST);

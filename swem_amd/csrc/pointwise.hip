@@ -4,6 +4,7 @@
 #include "../../include/swem_hip_train.h"
 #include "common.h"
 #include "bf16_split.h"
+#include "image_sample.h"
 
 namespace {
 
@@ -287,8 +288,6 @@ __global__ void resize_planes_kernel(const float *__restrict__ x, float *__restr
 }
 
 // ATen upsample_bicubic2d (align_corners=False, A = -0.75): unclamped source coordinate, 4x4 taps clamped to the image
-__device__ __forceinline__ float cubic1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
-__device__ __forceinline__ float cubic2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
 __global__ void resize_bicubic_kernel(const float *__restrict__ x, float *__restrict__ y, int planes, int Hi, int Wi,
                                       int Ho, int Wo) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -298,26 +297,13 @@ __global__ void resize_bicubic_kernel(const float *__restrict__ x, float *__rest
   int oy = (int)(t % Ho);
   long long pl = t / Ho;
   const float *src = x + pl * Hi * Wi;
-  const float A = -0.75f;
   const float sy = (float)Hi / (float)Ho * (oy + 0.5f) - 0.5f, sx = (float)Wi / (float)Wo * (ox + 0.5f) - 0.5f;
   const float fy = floorf(sy), fx = floorf(sx);
-  const int iy = (int)fy, ix = (int)fx;
-  const float ty = sy - fy, tx = sx - fx;
-  const float wy[4] = {cubic2(ty + 1.f, A), cubic1(ty, A), cubic1(1.f - ty, A), cubic2(2.f - ty, A)};
-  const float wx[4] = {cubic2(tx + 1.f, A), cubic1(tx, A), cubic1(1.f - tx, A), cubic2(2.f - tx, A)};
-  float acc = 0.f;
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    const int yy = min(max(iy - 1 + a, 0), Hi - 1);
-    float row = 0.f;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int xx = min(max(ix - 1 + b, 0), Wi - 1);
-      row += wx[b] * src[(long long)yy * Wi + xx];
-    }
-    acc += wy[a] * row;
-  }
-  y[i] = acc;
+  float wy[4], wx[4], acc[1];
+  cubic_weights<true>(sy - fy, wy);   // <true> and <1, 3>: this kernel's own roundings (image_sample.h)
+  cubic_weights(sx - fx, wx);
+  cubic_accumulate<1, 3>((int)fx, (int)fy, Wi, Hi, wx, wy, [&](int yy, int xx, float v[1]) { v[0] = src[(long long)yy * Wi + xx]; }, acc);
+  y[i] = acc[0];
 }
 // horizontal flip of planes (torch.flip(dims=[-1]), swem_evaluator.py:46-49)
 __global__ void flip_w_kernel(const float *__restrict__ x, float *__restrict__ y, long long rows, int W) {

@@ -1,9 +1,9 @@
 // Evaluation staging from decoded bytes (include/swem_hip_io.h): four pointwise, memory-bound kernels either side of the
 // timed loop.  Bytes come in (RGB frames, palette-PNG index maps), fp32 inputs / result bytes go out; the host touches no
 // pixel.
-//   stage_frames_kernel   uint8 HWC -> fp32 CHW in [0,1], bicubic-resized: b / 255 correctly rounded, then the arithmetic of
-//                         resize_bicubic_kernel (pointwise.hip) in its operation order; one thread per output pixel forms the
-//                         taps and weights once for the three channels
+//   stage_frames_kernel   uint8 HWC -> fp32 CHW in [0,1], bicubic-resized: b / 255 correctly rounded, then the cubic of
+//                         image_sample.h in resize_bicubic_kernel's operation order, every step fused; one thread per output
+//                         pixel forms the taps and weights once for the three channels
 //   onehot_kernel         index map + 256-entry channel table -> (C,H,W) fp32 one-hot; four pixels per thread
 //   pack_lut_kernel       int64 index maps -> uint8 object ids through a table (map_mask fused with pack_u8); 16 per thread;
 //                         a table of up to 32 ids is four 64-bit words in registers, a longer one is read from the arguments
@@ -12,6 +12,7 @@
 // The 256-entry tables travel in the launch itself (kernel arguments by value): no device allocation, no copy to wait for.
 // The only LDS is the four words that join a block's wave minima in overlay_min_kernel.
 #include "common.h"
+#include "image_sample.h"
 #include "../../include/swem_hip_io.h"
 
 namespace {
@@ -22,10 +23,6 @@ struct Table256 {
 struct Palette {
   unsigned char rgb[768];
 };
-
-// ATen upsample_bicubic2d coefficients (A = -0.75), as cubic1 / cubic2 of pointwise.hip
-__device__ __forceinline__ float st_cubic1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
-__device__ __forceinline__ float st_cubic2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
 
 // src [T][Hi][Wi][3] uint8 -> dst [T][3][Ho][Wo] fp32
 __global__ __launch_bounds__(256) void stage_frames_kernel(const unsigned char *__restrict__ src, float *__restrict__ dst,
@@ -38,30 +35,16 @@ __global__ __launch_bounds__(256) void stage_frames_kernel(const unsigned char *
   const int oy = (int)(r % Ho);
   const long long t = r / Ho;
   const unsigned char *img = src + t * Hi * Wi * 3;
-  const float A = -0.75f;
   const float sy = (float)Hi / (float)Ho * (oy + 0.5f) - 0.5f, sx = (float)Wi / (float)Wo * (ox + 0.5f) - 0.5f;
   const float fy = floorf(sy), fx = floorf(sx);
-  const int iy = (int)fy, ix = (int)fx;
-  const float ty = sy - fy, tx = sx - fx;
-  const float wy[4] = {st_cubic2(ty + 1.f, A), st_cubic1(ty, A), st_cubic1(1.f - ty, A), st_cubic2(2.f - ty, A)};
-  const float wx[4] = {st_cubic2(tx + 1.f, A), st_cubic1(tx, A), st_cubic1(1.f - tx, A), st_cubic2(2.f - tx, A)};
-  int xx[4];
+  float wy[4], wx[4], acc[3];
+  cubic_weights(sy - fy, wy);
+  cubic_weights(sx - fx, wx);
+  cubic_accumulate<3, 0>((int)fx, (int)fy, Wi, Hi, wx, wy, [&](int yy, int xx, float v[3]) {
+    const unsigned char *p = img + (long long)yy * Wi * 3 + xx * 3;
 #pragma unroll
-  for (int b = 0; b < 4; ++b) xx[b] = min(max(ix - 1 + b, 0), Wi - 1) * 3;
-  float acc[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    const int yy = min(max(iy - 1 + a, 0), Hi - 1);
-    const unsigned char *row = img + (long long)yy * Wi * 3;
-    float rs[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) rs[c] += wx[b] * __fdiv_rn((float)row[xx[b] + c], 255.0f);
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) acc[c] += wy[a] * rs[c];
-  }
+    for (int c = 0; c < 3; ++c) v[c] = __fdiv_rn((float)p[c], 255.0f);
+  }, acc);
   float *o = dst + t * 3 * plane + (long long)oy * Wo + ox;
 #pragma unroll
   for (int c = 0; c < 3; ++c) o[c * plane] = acc[c];

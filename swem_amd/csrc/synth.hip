@@ -1,7 +1,7 @@
 // Stage-0 training clips from static images: synthesis_frames of the reference (datasets/static_dataset.py:82-147) on the device
 // (include/swem_hip_data.h; DESIGN.md section 9 defines the arithmetic).
 //
-//   synth_clear_kernel      zeroes the statistics.  A launch, not a memset node: in a replay of the captured stage-0 call the
+//   clear_words_kernel      (image_sample.h) zeroes the statistics.  A launch, not a memset node: in a replay of the captured stage-0 call the
 //                           memset node left the buffer filled with a stale 8-byte pattern instead of zeros (B = 4, N = 2, 480x640
 //                           slots), and these words become addresses.  The static chain's entry clears its
 //                           presence set the same way: a captured stage-0 call holds no memset node.
@@ -14,6 +14,7 @@
 //                           of the boxed image, taps clamped to the box; no hit: image 0, its own object painted with its mean colour.
 // Every size and index that comes from the parameter block is clamped on the device: a wrong block gives wrong pictures, no fault.
 #include "common.h"
+#include "image_sample.h"
 #include "../../include/swem_hip_data.h"
 
 namespace {
@@ -34,15 +35,6 @@ inline SynthLayout synth_layout(int B, int T, int N) {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
-// the project's cubic (pointwise.hip, ATen's upsample_bicubic2d: A = -0.75)
-__device__ __forceinline__ float syn_cubic1(float x) { return (1.25f * x - 2.25f) * x * x + 1.f; }
-__device__ __forceinline__ float syn_cubic2(float x) { return ((-0.75f * x + 3.75f) * x - 6.f) * x + 3.f; }
-
-__global__ __launch_bounds__(256) void synth_clear_kernel(unsigned *__restrict__ stats, int n) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) stats[i] = 0u;
-}
-
 __global__ __launch_bounds__(256) void synth_stats_kernel(const unsigned char *__restrict__ imgs,
                                                           const unsigned char *__restrict__ masks,
                                                           const int *__restrict__ params, unsigned *__restrict__ stats, int N,
@@ -50,9 +42,9 @@ __global__ __launch_bounds__(256) void synth_stats_kernel(const unsigned char *_
   __shared__ unsigned red[4][SWEM_SYNTH_STAT_WORDS];
   const int tile = blockIdx.x, k = blockIdx.y, b = blockIdx.z;
   const int *C = params + (size_t)b * SWEM_SYNTH_CLIP_WORDS;
-  const int n_img = clampi(C[0], 1, N);
+  const int n_img = clampi(C[SWEM_SYNTH_N_IMG], 1, N);
   if (k >= n_img) return;                                   // (the whole block)
-  const int h = clampi(C[2 + 2 * k], 1, Hmax), w = clampi(C[3 + 2 * k], 1, Wmax);
+  const int h = clampi(C[SWEM_SYNTH_SIZES + 2 * k], 1, Hmax), w = clampi(C[SWEM_SYNTH_SIZES + 2 * k + 1], 1, Wmax);
   const int x = (tile % tiles_x) * SYN_TW + (threadIdx.x & (SYN_TW - 1));
   const int y = (tile / tiles_x) * SYN_TH + (threadIdx.x / SYN_TW);
   unsigned v[SWEM_SYNTH_STAT_WORDS] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
@@ -60,31 +52,32 @@ __global__ __launch_bounds__(256) void synth_stats_kernel(const unsigned char *_
     const size_t px = (((size_t)b * N + k) * Hmax + y) * Wmax + x;
     if (masks[px] != 0) {
       const unsigned char *p = imgs + px * 3;
-      v[0] = ~(unsigned)y;
-      v[1] = ~(unsigned)x;
-      v[2] = (unsigned)y + 1u;
-      v[3] = (unsigned)x + 1u;
-      v[4] = 1u;
-      v[5] = p[0];
-      v[6] = p[1];
-      v[7] = p[2];
+      v[SWEM_SYNTH_STAT_NOT_HMIN] = ~(unsigned)y;
+      v[SWEM_SYNTH_STAT_NOT_WMIN] = ~(unsigned)x;
+      v[SWEM_SYNTH_STAT_HMAX1] = (unsigned)y + 1u;
+      v[SWEM_SYNTH_STAT_WMAX1] = (unsigned)x + 1u;
+      v[SWEM_SYNTH_STAT_COUNT] = 1u;
+      v[SWEM_SYNTH_STAT_SUM_R] = p[0];
+      v[SWEM_SYNTH_STAT_SUM_G] = p[1];
+      v[SWEM_SYNTH_STAT_SUM_B] = p[2];
     }
   }
+  // the words before COUNT are built by max, COUNT and the sums by add
   for (int off = 32; off > 0; off >>= 1) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = max(v[q], (unsigned)__shfl_down((int)v[q], off));
+    for (int q = 0; q < SWEM_SYNTH_STAT_COUNT; ++q) v[q] = max(v[q], (unsigned)__shfl_down((int)v[q], off));
 #pragma unroll
-    for (int q = 4; q < 8; ++q) v[q] += (unsigned)__shfl_down((int)v[q], off);
+    for (int q = SWEM_SYNTH_STAT_COUNT; q < SWEM_SYNTH_STAT_WORDS; ++q) v[q] += (unsigned)__shfl_down((int)v[q], off);
   }
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-    for (int q = 0; q < 8; ++q) red[threadIdx.x >> 6][q] = v[q];
+    for (int q = 0; q < SWEM_SYNTH_STAT_WORDS; ++q) red[threadIdx.x >> 6][q] = v[q];
   }
   __syncthreads();
   if (threadIdx.x < SWEM_SYNTH_STAT_WORDS) {
     const int q = threadIdx.x;
     unsigned *S = stats + ((size_t)b * N + k) * SWEM_SYNTH_STAT_WORDS + q;
-    if (q < 4) {
+    if (q < SWEM_SYNTH_STAT_COUNT) {
       const unsigned m = max(max(red[0][q], red[1][q]), max(red[2][q], red[3][q]));
       if (m) atomicMax(S, m);
     } else {
@@ -101,17 +94,18 @@ __global__ __launch_bounds__(64) void synth_plan_kernel(const int *__restrict__ 
   const int k = idx % N, t = (idx / N) % T, b = idx / (N * T);
   const int *C = params + (size_t)b * SWEM_SYNTH_CLIP_WORDS;
   const int *F = params + (size_t)B * SWEM_SYNTH_CLIP_WORDS + ((size_t)b * T + t) * SWEM_SYNTH_FRAME_WORDS;
-  const float *FF = reinterpret_cast<const float *>(F);
+  const float *O = reinterpret_cast<const float *>(F) + SWEM_SYNTH_OBJECTS + 4 * k;   // area, aspect, ux, uy
   const unsigned *S = stats + ((size_t)b * N + k) * SWEM_SYNTH_STAT_WORDS;
   int *P = plan + (size_t)idx * SWEM_SYNTH_PLAN_WORDS;
-  const int n_img = clampi(C[0], 1, N);
-  const int h0 = clampi(C[2], 1, Hmax), w0 = clampi(C[3], 1, Wmax);
+  const int n_img = clampi(C[SWEM_SYNTH_N_IMG], 1, N);
+  const int h0 = clampi(C[SWEM_SYNTH_SIZES], 1, Hmax), w0 = clampi(C[SWEM_SYNTH_SIZES + 1], 1, Wmax);
   int rh = 0, rw = 0, tx = 0, ty = 0, present = 0;
-  if (k < n_img && S[4] != 0u) {
+  if (k < n_img && S[SWEM_SYNTH_STAT_COUNT] != 0u) {
     present = 1;
-    const double hc = (double)(S[2] - ~S[0]), wc = (double)(S[3] - ~S[1]);
-    const double area = (double)FF[8 + 4 * k] * hc * wc, aspect = (double)FF[9 + 4 * k];
-    const double ux = (double)FF[10 + 4 * k], uy = (double)FF[11 + 4 * k];
+    const double hc = (double)(S[SWEM_SYNTH_STAT_HMAX1] - ~S[SWEM_SYNTH_STAT_NOT_HMIN]);
+    const double wc = (double)(S[SWEM_SYNTH_STAT_WMAX1] - ~S[SWEM_SYNTH_STAT_NOT_WMIN]);
+    const double area = (double)O[0] * hc * wc, aspect = (double)O[1];
+    const double ux = (double)O[2], uy = (double)O[3];
     // (a NaN or a huge value from a wrong block must not reach the cast: sizes stay within 4 slots)
     const double dh = fmin(fmax(rint(sqrt(area / aspect)), 1.0), 4.0 * Hmax), dw = fmin(fmax(rint(sqrt(area * aspect)), 1.0), 4.0 * Wmax);
     rh = dh == dh ? (int)dh : 1;
@@ -122,14 +116,13 @@ __global__ __launch_bounds__(64) void synth_plan_kernel(const int *__restrict__ 
     tx = sx == sx ? (int)sx : 0;      // cx - rw/2 with cx = lo + ...
     ty = sy == sy ? (int)sy : 0;
   }
-  P[0] = rh;
-  P[1] = rw;
-  P[2] = tx;
-  P[3] = ty;
-  P[4] = k < n_img ? (C[16 + k] & 255) : 0;
-  P[5] = present;
-  P[6] = 0;
-  P[7] = 0;
+  P[SWEM_SYNTH_PLAN_RH] = rh;
+  P[SWEM_SYNTH_PLAN_RW] = rw;
+  P[SWEM_SYNTH_PLAN_TX] = tx;
+  P[SWEM_SYNTH_PLAN_TY] = ty;
+  P[SWEM_SYNTH_PLAN_ID] = k < n_img ? (C[SWEM_SYNTH_IDS + k] & 255) : 0;
+  P[SWEM_SYNTH_PLAN_PRESENT] = present;
+  for (int q = SWEM_SYNTH_PLAN_PRESENT + 1; q < SWEM_SYNTH_PLAN_WORDS; ++q) P[q] = 0;
 }
 
 struct SynObj {
@@ -148,38 +141,38 @@ __global__ __launch_bounds__(256) void synth_composite_kernel(const unsigned cha
   const int tile = blockIdx.x, t = blockIdx.y, b = blockIdx.z;
   const int *C = params + (size_t)b * SWEM_SYNTH_CLIP_WORDS;
   const int *F = params + (size_t)B * SWEM_SYNTH_CLIP_WORDS + ((size_t)b * T + t) * SWEM_SYNTH_FRAME_WORDS;
-  const int n_img = clampi(C[0], 1, N);
-  const int h0 = clampi(C[2], 1, Hmax), w0 = clampi(C[3], 1, Wmax);
+  const int n_img = clampi(C[SWEM_SYNTH_N_IMG], 1, N);
+  const int h0 = clampi(C[SWEM_SYNTH_SIZES], 1, Hmax), w0 = clampi(C[SWEM_SYNTH_SIZES + 1], 1, Wmax);
   if (threadIdx.x == 0) {
     int n = 0;
     for (int p = n_img - 1; p >= 0; --p) {
-      const int k = F[p];
+      const int k = F[SWEM_SYNTH_PASTE + p];
       if (k < 0 || k >= n_img) continue;
       const int *P = plan + (((size_t)b * T + t) * N + k) * SWEM_SYNTH_PLAN_WORDS;
-      if (!P[5]) continue;
+      if (!P[SWEM_SYNTH_PLAN_PRESENT]) continue;
       const unsigned *S = stats + ((size_t)b * N + k) * SWEM_SYNTH_STAT_WORDS;
       // The box and the placement become addresses below.  They are this call's own words, but the workspace is the caller's memory:
       // whatever it holds when this block reads it (a second call on another stream sharing it, a stale or half-built table), the
       // box stays inside the slot and the sizes positive -- wrong words give a wrong picture, never an access outside the slot.
       SynObj o;
       o.k = k;
-      o.rh = P[0];
-      o.rw = P[1];
+      o.rh = P[SWEM_SYNTH_PLAN_RH];
+      o.rw = P[SWEM_SYNTH_PLAN_RW];
       if (o.rh < 1 || o.rw < 1) continue;
-      o.tx = clampi(P[2], 0, Wmax);
-      o.ty = clampi(P[3], 0, Hmax);
-      o.id = P[4];
-      o.hmin = clampi((int)~S[0], 0, Hmax - 1);
-      o.wmin = clampi((int)~S[1], 0, Wmax - 1);
-      o.hc = clampi((int)S[2] - o.hmin, 1, Hmax - o.hmin);
-      o.wc = clampi((int)S[3] - o.wmin, 1, Wmax - o.wmin);
+      o.tx = clampi(P[SWEM_SYNTH_PLAN_TX], 0, Wmax);
+      o.ty = clampi(P[SWEM_SYNTH_PLAN_TY], 0, Hmax);
+      o.id = P[SWEM_SYNTH_PLAN_ID];
+      o.hmin = clampi((int)~S[SWEM_SYNTH_STAT_NOT_HMIN], 0, Hmax - 1);
+      o.wmin = clampi((int)~S[SWEM_SYNTH_STAT_NOT_WMIN], 0, Wmax - 1);
+      o.hc = clampi((int)S[SWEM_SYNTH_STAT_HMAX1] - o.hmin, 1, Hmax - o.hmin);
+      o.wc = clampi((int)S[SWEM_SYNTH_STAT_WMAX1] - o.wmin, 1, Wmax - o.wmin);
       obj[n++] = o;
     }
     nobj = n;
   }
   if (threadIdx.x < 3) {
     const unsigned *S = stats + (size_t)b * N * SWEM_SYNTH_STAT_WORDS;
-    const double m = (double)S[5 + threadIdx.x] / ((double)S[4] + 1e-8);
+    const double m = (double)S[SWEM_SYNTH_STAT_SUM_R + threadIdx.x] / ((double)S[SWEM_SYNTH_STAT_COUNT] + 1e-8);
     mean_fg[threadIdx.x] = (unsigned char)floor(fmin(fmax(m, 0.0), 255.0) + 0.5);
   }
   __syncthreads();
@@ -205,32 +198,14 @@ __global__ __launch_bounds__(256) void synth_composite_kernel(const unsigned cha
     if (masks[(base + o.hmin + k_my) * Wmax + o.wmin + k_mx] == 0) continue;
     const double bx = ((double)dx + 0.5) * (double)o.wc / (double)o.rw - 0.5, by = ((double)dy + 0.5) * (double)o.hc / (double)o.rh - 0.5;
     const double fx = floor(bx), fy = floor(by);
-    const int ix = (int)fx, iy = (int)fy;
-    const float ax = (float)(bx - fx), ay = (float)(by - fy);
-    const float wx[4] = {syn_cubic2(ax + 1.f), syn_cubic1(ax), syn_cubic1(1.f - ax), syn_cubic2(2.f - ax)};
-    const float wy[4] = {syn_cubic2(ay + 1.f), syn_cubic1(ay), syn_cubic1(1.f - ay), syn_cubic2(2.f - ay)};
-    int xo[4];
+    float wx[4], wy[4], acc[3];
+    cubic_weights((float)(bx - fx), wx);
+    cubic_weights((float)(by - fy), wy);
+    cubic_accumulate<3, 0>((int)fx, (int)fy, o.wc, o.hc, wx, wy, [&](int yy, int xx, float tap[3]) {
+      rgb_bytes(imgs + (base + o.hmin + yy) * Wmax * 3 + 3 * (o.wmin + xx), tap);
+    }, acc);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) xo[c] = 3 * (o.wmin + clampi(ix - 1 + c, 0, o.wc - 1));
-    float r = 0.f, g = 0.f, bl = 0.f;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const unsigned char *row = imgs + (base + o.hmin + clampi(iy - 1 + a, 0, o.hc - 1)) * Wmax * 3;
-      float rr = 0.f, rg = 0.f, rb = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const unsigned char *p = row + xo[c];
-        rr += wx[c] * (float)p[0];
-        rg += wx[c] * (float)p[1];
-        rb += wx[c] * (float)p[2];
-      }
-      r += wy[a] * rr;
-      g += wy[a] * rg;
-      bl += wy[a] * rb;
-    }
-    comp[out * 3 + 0] = (unsigned char)floorf(fminf(fmaxf(r, 0.f), 255.f) + 0.5f);
-    comp[out * 3 + 1] = (unsigned char)floorf(fminf(fmaxf(g, 0.f), 255.f) + 0.5f);
-    comp[out * 3 + 2] = (unsigned char)floorf(fminf(fmaxf(bl, 0.f), 255.f) + 0.5f);
+    for (int c = 0; c < 3; ++c) comp[out * 3 + c] = (unsigned char)floorf(fminf(fmaxf(acc[c], 0.f), 255.f) + 0.5f);
     comp_lab[out] = (unsigned char)o.id;
     return;
   }
@@ -269,7 +244,7 @@ extern "C" int swem_synth_frames_u8(void *stream, const unsigned char *imgs, con
   unsigned *stats = reinterpret_cast<unsigned *>(w + L.stats);
   int *plan = reinterpret_cast<int *>(w + L.plan);
   const int nstat = B * N * SWEM_SYNTH_STAT_WORDS;
-  hipLaunchKernelGGL(synth_clear_kernel, dim3((unsigned)cdiv(nstat, 256)), dim3(256), 0, ST, stats, nstat);
+  hipLaunchKernelGGL(clear_words_kernel, dim3((unsigned)cdiv(nstat, 256)), dim3(256), 0, ST, stats, nstat);
   SWEM_CHECK_LAUNCH("synth_clear");
   const int tiles_x = cdiv(Wmax, SYN_TW), tiles = tiles_x * cdiv(Hmax, SYN_TH);
   const int *par = static_cast<const int *>(params);

@@ -1466,7 +1466,8 @@ def augment_clips(src, lab, params, frames, masks, valid, label, found, ws, b0=0
                                 % tuple(tuple(t.shape) for t in (src, lab, frames, masks, valid, label, found)))
     if not (0 <= b0 and b0 + B <= Bo):
         raise _lib.SwemHipError('augment_clips: clips %d..%d do not fit a batch of %d' % (b0, b0 + B - 1, Bo))
-    words = B * T * 64 + B * 256
+    from .augment import frame_block_words
+    words = frame_block_words(B, T)
     if not (params.is_cuda and params.is_contiguous() and params.element_size() == 4 and params.numel() >= words):
         raise _lib.SwemHipError('augment_clips: params must be a contiguous device block of %d 32-bit words' % words)
     _lib.call(entry, _stream(), src.data_ptr(), lab.data_ptr(), params.data_ptr(), frames[b0:].data_ptr(),
@@ -1495,7 +1496,8 @@ def synth_frames(imgs, masks, params, comp, comp_lab, ws):
     if tuple(imgs.shape) != (B, N, Hm, Wm, 3) or tuple(comp_lab.shape) != (B, T, Hm, Wm) or tuple(comp.shape) != (B, T, Hm, Wm, 3):
         raise _lib.SwemHipError('synth_frames: inconsistent shapes imgs %s masks %s comp %s comp_lab %s'
                                 % tuple(tuple(t.shape) for t in (imgs, masks, comp, comp_lab)))
-    words = B * 32 + B * T * 64
+    from .augment import synth_block_words
+    words = synth_block_words(B, T)
     if not (params.is_cuda and params.is_contiguous() and params.element_size() == 4 and params.numel() >= words):
         raise _lib.SwemHipError('synth_frames: params must be a contiguous device block of %d 32-bit words' % words)
     _lib.call('swem_synth_frames_u8', _stream(), imgs.data_ptr(), masks.data_ptr(), params.data_ptr(), comp.data_ptr(),

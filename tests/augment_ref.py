@@ -11,6 +11,7 @@ measurement (tools/augment_parity.py) and the benchmark share.
 import numpy as np
 
 from swem_amd import augment as A
+from tests.io_ref import cubic_weights as _cubic_weights
 
 EDGE = 1e-3        # px: a pixel whose float64 coordinate is this close to a threshold is excluded from the comparison
 LABEL_VALUES = (0, 3, 7, 12, 255)
@@ -65,17 +66,6 @@ def near_threshold(g, out_hw, edge=EDGE):
 
 
 # ---------------------------------------------------------------------------------------------------------------- sampling
-def _cubic_weights(t, f, a=-0.75):
-    a = f(a)
-
-    def c1(x):
-        return ((a + f(2)) * x - (a + f(3))) * x * x + f(1)
-
-    def c2(x):
-        return ((a * x - f(5) * a) * x + f(8) * a) * x - f(4) * a
-    return [c2(t + f(1)), c1(t), c1(f(1) - t), c2(f(2) - t)]
-
-
 def sample(src, lab, g, dtype=np.float64):
     """Step 4: (img (3,Ho,Wo) before any colour op, label (Ho,Wo) uint8, region (Ho,Wo) uint8)."""
     f = dtype

@@ -138,20 +138,25 @@ def input_size(h, w, short_size=495):
 
 
 # ------------------------------------------------------------------------------------------------------------- frames
+def cubic_weights(t, f, a=-0.75):
+    """The four cubic weights of the fraction t in dtype f: the one cubic of the test references (tests/augment_ref.py and
+    tests/synth_ref.py sample with it too)."""
+    a = f(a)
+
+    def c1(x):
+        return ((a + f(2)) * x - (a + f(3))) * x * x + f(1)
+
+    def c2(x):
+        return ((a * x - f(5) * a) * x + f(8) * a) * x - f(4) * a
+    return [c2(t + f(1)), c1(t), c1(f(1) - t), c2(f(2) - t)]
+
+
 def _cubic_matrix(n_in, n_out):
     """(n_out, n_in) float64: ATen's upsample_bicubic2d along one axis, align_corners=False, A = -0.75, taps clamped."""
-    A = -0.75
     o = np.arange(n_out, dtype=np.float64)
     s = (n_in / n_out) * (o + 0.5) - 0.5
     f = np.floor(s)
-    t = s - f
-
-    def c1(x):
-        return ((A + 2) * x - (A + 3)) * x * x + 1
-
-    def c2(x):
-        return ((A * x - 5 * A) * x + 8 * A) * x - 4 * A
-    w = np.stack([c2(t + 1), c1(t), c1(1 - t), c2(2 - t)], 1)
+    w = np.stack(cubic_weights(s - f, np.float64), 1)
     m = np.zeros((n_out, n_in), np.float64)
     for k in range(4):
         idx = np.clip(f.astype(np.int64) - 1 + k, 0, n_in - 1)

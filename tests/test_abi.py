@@ -25,6 +25,30 @@ def test_header_symbols_are_exported_and_bound(lib):
     assert sorted(_lib.SIGNATURES) == syms, 'binding lists symbols the header does not declare'
 
 
+def declared_record_words():
+    """Every enumerator and every SWEM_*_WORDS / SWEM_*_MAX_* define of swem_hip_data.h, without the SWEM_ prefix."""
+    src = re.sub(r'/\*.*?\*/', '', open(os.path.join(INCLUDE, 'swem_hip_data.h')).read(), flags=re.S)
+    words = {n: int(v) for n, v in re.findall(r'^#define\s+SWEM_(\w+_WORDS|\w+_MAX_\w+)\s+(\d+)\s*$', src, flags=re.M)}
+    for body in re.findall(r'\benum\s*\{(.*?)\}', src, flags=re.S):
+        for n, v in re.findall(r'\bSWEM_(\w+)\s*=\s*(\d+)', body):
+            assert n not in words, n
+            words[n] = int(v)
+        assert len(re.findall(r'\bSWEM_\w+', body)) == len(re.findall(r'\bSWEM_\w+\s*=\s*\d+', body)), 'an enumerator without a value'
+    return words
+
+
+def test_record_words_of_the_data_header_equal_the_python_table():
+    """swem_amd/augment.py packs and reads the parameter records, statistics and placement words by the names of
+    include/swem_hip_data.h: both sides hold the same names with the same values."""
+    from swem_amd import augment as A
+    header = declared_record_words()
+    table = {k: v for k, v in vars(A.Rec).items() if k.isupper()}
+    assert len(header) >= 48 and header['AUG_HUE'] == 63 and header['SYNTH_IDS'] == 16 and header['AUG_FRAME_WORDS'] == 64
+    assert sorted(table) == sorted(header)
+    for name in header:
+        assert table[name] == header[name], name
+
+
 def test_version_and_error_channel(lib):
     assert lib.swem_version() == 2      # round 5: explicit fault-word arguments
     # argument validation happens before any HIP call, so it can be exercised without a GPU

@@ -190,6 +190,25 @@ def test_parity_cases_keep_the_exclusion_set_under_the_cap_and_the_recorded_bars
     assert 4.0 * rec['cases']['full_384']['fp32_vs_fp64_max'] == rec['cases']['full_384']['bar']
 
 
+# ---------------------------------------------------------------------------------------------- workspace layouts
+def test_python_layouts_end_where_the_workspace_queries_do(lib):
+    """augment_layout / synth_layout restate aug_layout (csrc/augment.hip) and synth_layout (csrc/synth.hip): the totals are the
+    C side's, the fields ascend, and the aligned ones sit on 256 bytes.  2x2: the smallest output; 21x40 and 24x33: partial tiles
+    on either axis."""
+    for B in (1, 2, 3):
+        for T in (1, 2, 3):
+            for Ho, Wo in ((2, 2), (21, 40), (24, 33)):
+                lay = A.augment_layout(B, T, Ho, Wo)
+                assert lay['total'] == lib.swem_augment_workspace(B, T, Ho, Wo), (B, T, Ho, Wo)
+                assert lay['wlab'] == 0 and lay['wreg'] == B * T * Ho * Wo
+                assert 2 * lay['wreg'] <= lay['presence'] < lay['partial'] < lay['total']
+                assert lay['presence'] % 256 == 0 and lay['partial'] % 256 == 0
+            for N in (1, 3, 7):
+                lay = A.synth_layout(B, T, N)
+                assert lay['total'] == lib.swem_synth_workspace(B, T, N), (B, T, N)
+                assert lay['stats'] == 0 and B * N * 32 <= lay['plan'] < lay['total'] and lay['plan'] % 256 == 0
+
+
 # ---------------------------------------------------------------------------------------------- C ABI: argument validation
 def test_augment_entry_points_validate_before_any_hip_call(lib):
     assert lib.swem_augment_workspace(0, 3, 24, 40) == 0 and lib.swem_augment_workspace(2, 3, 24, -1) == 0

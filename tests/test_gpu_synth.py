@@ -327,7 +327,7 @@ def test_eager_calls_and_graph_replays_are_bit_identical():
 
 def test_graph_replay_of_four_clips_equals_the_eager_call():
     """B = 4, N = 2: the batch at which a captured call that cleared its words with memset nodes replayed with a buffer mis-filled
-    (csrc/synth.hip, synth_clear_kernel).  The replay is compared without refilling the parameters, statistics and table included."""
+    (csrc/image_sample.h, clear_words_kernel).  The replay is compared without refilling the parameters, statistics and table included."""
     sizes = S.CASES['n2_24x40'][3] * 2
     imgs, masks = S.make_slots(28, sizes, 2)
     rng = np.random.default_rng(29)

@@ -73,8 +73,8 @@ def main():
     torch.cuda.synchronize()
     comp, comp_lab = syn.composites(B)
     first = [t.clone() for t in out] + [comp.clone(), comp_lab.clone()]
-    ws, dev = syn._buffers(B)[:2]
-    sws, sdev = syn._synth_buffers(B)[:2]
+    ws, dev = syn._buffers(B).ws, syn._buffers(B).params.dev
+    sws, sdev = syn._synth_buffers(B).ws, syn._synth_buffers(B).params.dev
 
     def eager():
         syn(i, m, None, out=out)
