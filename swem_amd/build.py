@@ -6,10 +6,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libswem_hip.so')
-SOURCES = ['api.hip', 'conv.hip', 'bneck.hip', 'pointwise.hip', 'em.hip', 'match.hip', 'train.hip', 'train_conv.hip', 'metrics.hip',
-           'augment.hip', 'synth.hip', 'stage.hip', 'png.hip']
-# (source, extra flags, object): conv.hip a second time for conv_t256_kernel alone (-DSWEM_CONV_T256_ONLY: csrc/conv.hip)
-EXTRA_UNITS = [('conv.hip', ['-DSWEM_CONV_T256_ONLY'], 'conv_t256.o')]
+# (conv_presplit.hip first: its five minutes are the critical path of a full build)
+SOURCES = ['conv_presplit.hip', 'api.hip', 'conv.hip', 'conv_f32.hip', 'conv_t256.hip', 'bneck.hip', 'pointwise.hip', 'em.hip',
+           'match.hip', 'train.hip', 'train_conv.hip', 'metrics.hip', 'augment.hip', 'synth.hip', 'stage.hip', 'png.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 
@@ -23,7 +22,7 @@ def _stale(target, deps):
 
 def _headers_of(path, seen=None):
     """The repo headers a source includes, transitively (`#include "..."` lines only): a unit is rebuilt when ONE OF ITS OWN
-    headers is newer than its object -- conv.hip (five minutes) does not include the training header."""
+    headers is newer than its object -- conv_presplit.hip (five minutes) does not include the training header."""
     import re
     seen = set() if seen is None else seen
     try:
@@ -47,20 +46,14 @@ def build(force=False, verbose=False):
         if force or _stale(o, [s] + sorted(_headers_of(s))):
             todo.append([HIPCC] + FLAGS + ['-c', s, '-o', o])
         objs.append(o)
-    for src, extra, obj in EXTRA_UNITS:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(CSRC, obj)
-        if force or _stale(o, [s] + sorted(_headers_of(s))):
-            todo.append([HIPCC] + FLAGS + extra + ['-c', s, '-o', o])
-        objs.append(o)
 
     def run(cmd):
         if verbose:
             print(' '.join(cmd))
         subprocess.check_call(cmd)
-    # the translation units are independent: compile the stale ones side by side (conv.hip alone takes ~5 minutes; the
-    # container has 8 CPUs -- SWEM_BUILD_JOBS overrides)
-    jobs = max(1, min(len(todo), int(os.environ.get('SWEM_BUILD_JOBS', '0')) or (os.cpu_count() or 1)))
+    # the translation units are independent: compile the stale ones side by side (conv_presplit.hip alone takes ~5 minutes).
+    # At most 16 jobs: os.cpu_count() is the whole machine's count on a shared host -- SWEM_BUILD_JOBS overrides
+    jobs = max(1, min(len(todo), int(os.environ.get('SWEM_BUILD_JOBS', '0')) or min(16, os.cpu_count() or 1)))
     if todo:
         with ThreadPoolExecutor(jobs) as ex:
             list(ex.map(run, todo))

@@ -3,7 +3,7 @@
 //     y = relu( bn3(conv1x1_{Cm->C}( relu(bn2(conv3x3_{Cm->Cm}( relu(bn1(conv1x1_{C->Cm}(x))) ))) )) + x ),      C = 4 Cm
 //
 // for the identity blocks of a stage (stride 1, no down-sampling branch), in the f16x3 arithmetic of the pre-split convolution
-// kernel (conv.hip): every operand an fp16 (hi, mid) pair, three products hi.mid + mid.hi + hi.hi on v_mfma_f32_16x16x32_f16,
+// kernel (conv_presplit.hip): every operand an fp16 (hi, mid) pair, three products hi.mid + mid.hi + hi.hi on v_mfma_f32_16x16x32_f16,
 // fp32 accumulation, frozen BatchNorm as per-filter scale / shift.  As three launches the block moves its input, its output
 // and two Cm-channel intermediates through memory four times over (1,059 MB for ten 480p frames) and runs at 0.3x of a plain
 // copy of its input planes to its output planes (profiles/r05_bottleneck_fusion_bound.json: 337 us against 101 us); here the
@@ -11,13 +11,13 @@
 //
 // Block = one 8 x 16 tile of output pixels of one image, 8 waves, one block per CU.  Three GEMM phases:
 //   1  y1 = relu(bn1(x . w1)) on the tile's 10 x 18 HALO patch (180 pixels, 192 LDS rows), K = C in 32-channel k-blocks: the
-//      x planes and w1 go L2 -> LDS by buffer_load ... lds through a two-stage ring exactly as in conv.hip (patch pixels outside
+//      x planes and w1 go L2 -> LDS by buffer_load ... lds through a two-stage ring exactly as in conv_presplit.hip (patch pixels outside
 //      the image use an out-of-range offset and land as zeros); y1 is split into its fp16 pair and kept in LDS, ZERO where the
 //      patch pixel lies outside the image (conv2's zero padding pads y1, not x);
 //   2  y2 = relu(bn2(conv3x3(y1))): K = 9 Cm, k-block = (32-channel block, tap); the A fragments are read from the y1 patch at
 //      the tap's row offset, w2 streams through a four-stage ring; y2 (128 pixels x Cm) stays in LDS as an fp16 pair;
 //   3  y = relu(bn3(y2 . w3) + x): w3 (64 KB as a pair) is loaded whole -- its second plane already during phase 2 --, K = Cm;
-//      the epilogue stages 32 x 32 sub-tiles per wave through the LDS and leaves in ROW layout (conv.hip, out_tile32): 16-byte
+//      the epilogue stages 32 x 32 sub-tiles per wave through the LDS and leaves in ROW layout (conv_common.h, out_tile32): 16-byte
 //      stores of y (optional) and of y's own fp16 pair planes, the residual read back from x's planes (hi + mid: the value to
 //      22-23 significant bits, exactly what the unfused path adds: swem_conv2d_nhwc_bf16x3_planes_res).
 // The k order of every GEMM and the order of the three products are the conv kernel's (M16 form), so the block agrees with the
@@ -48,7 +48,7 @@ struct BneckP {
 __device__ __forceinline__ f32x4v mm(uint4 a, uint4 b, f32x4v c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
-__device__ __forceinline__ float relu_(float x) {   // one v_max_f32 (conv.hip, relu1)
+__device__ __forceinline__ float relu_(float x) {   // one v_max_f32 (conv_common.h, relu1)
   float y;
   asm("v_max_f32 %0, 0, %1" : "=v"(y) : "v"(x));
   return y;
@@ -72,11 +72,11 @@ __device__ __forceinline__ void pair16(float v, unsigned short &h, unsigned shor
 }
 
 constexpr int TH = 8, TW = 16, PW = TW + 2, PP = (TH + 2) * (TW + 2), PR = 192;   // tile, patch width / pixels / LDS rows
-constexpr int PL_STRIDE_B = 36;                    // dwords per staged epilogue row (conv.hip)
+constexpr int PL_STRIDE_B = 36;                    // dwords per staged epilogue row (conv_common.h)
 constexpr int PL_BYTES_B = 32 * PL_STRIDE_B * 4;   // epilogue staging bytes per wave
 
 // LDS map (Cm = 64: exactly the CU's 160 KB).  One block per CU, so nothing but the block's own ring depth hides the L2 -> LDS
-// latency (conv.hip leans on its second resident block for that): every phase uses ALL the LDS that is dead at the time.
+// latency (conv_presplit.hip leans on its second resident block for that): every phase uses ALL the LDS that is dead at the time.
 //   [0, 64K)      R   phase 1: ring stages 0-1        phase 2-3: w3, whole (requested at the start of phase 2)
 //   [64K, 112K)   Y1  phase 1: ring stages 2-3 (part) phase 2: the y1 patch               phase 3: epilogue staging
 //   [112K, 144K)  Y2  phase 1: ring stage 3 (part)    phase 2: w2 ring stages 0-3         phase 3: y2
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(512, 1) void bneck_kernel(BneckP p STAMP_ARG) {
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc1[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
-  // ring of NS1 stages, NS1 - 1 k-blocks in flight (4 transfers per wave and k-block): conv.hip's counted-wait hand-over
+  // ring of NS1 stages, NS1 - 1 k-blocks in flight (4 transfers per wave and k-block): conv_presplit.hip's counted-wait hand-over
 #pragma unroll
   for (int d = 0; d < L::NS1 - 1; ++d) issue1(d, d);
   wait_vm(4 * (L::NS1 - 2));        // k-block 0 has landed; the younger ones may stay in flight

@@ -1,4 +1,4 @@
-// LDS-DMA helpers shared by the convolution kernels (forward / data gradient: conv.hip; weight gradient: train_conv.hip).
+// LDS-DMA helpers shared by the convolution kernels (forward / data gradient: conv_presplit.hip, conv_t256.hip; weight gradient: train_conv.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

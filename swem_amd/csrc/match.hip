@@ -350,7 +350,7 @@ __global__ __launch_bounds__(512) void match_affinity16_kernel(const float *__re
   }
   if (pq) {
     // the same probabilities (times 2^14) as the readout GEMM's pre-split operand: fp16 planes hi / mid, [plane][Ltot/8][N*Pm][8]
-    // (conv.hip's activation layout).  The lane's four bases are half of an 8-channel group: 8 bytes per plane and tile,
+    // (conv_presplit.hip's activation layout).  The lane's four bases are half of an 8-channel group: 8 bytes per plane and tile,
     // the 16 pixels x 2 halves of a group one contiguous 256-byte run.
     const long long npix = (long long)gridDim.y * Pm, gp = (long long)n * Pm + p;
     unsigned short *d0 = pq + (((long long)(wave * 2 * TW + (g >> 1)) * npix + gp) * 8 + 4 * (g & 1));

@@ -78,7 +78,7 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
         _lib.load()
 
 
-@pytest.mark.skipif(not os.environ.get('SWEM_SLOW_TESTS'), reason='the FULL ISA check of conv.hip takes ~5 minutes: nightly (SWEM_SLOW_TESTS=1)')
+@pytest.mark.skipif(not os.environ.get('SWEM_SLOW_TESTS'), reason='the FULL ISA check of conv_presplit.hip takes ~5 minutes: nightly (SWEM_SLOW_TESTS=1)')
 def test_lds_dma_kernels_are_the_only_m0_users_every_instantiation():
     """The check below on EVERY instantiation of conv_igemm_bf3s_kernel (stream-K, one- and three-plane kernels, the four-stage and
     prefetched-fragment variants): the default run compiles a fifth of them (-DSWEM_ISA_SUBSET) to stay within a minute, so an
@@ -87,7 +87,8 @@ def test_lds_dma_kernels_are_the_only_m0_users_every_instantiation():
 
 
 def test_lds_dma_kernels_are_the_only_m0_users():
-    """conv.hip issues buffer_load ... lds from inline asm and writes M0 itself, without saving it (csrc/conv.hip, dma16).
+    """conv_presplit.hip and conv_t256.hip issue buffer_load ... lds from inline asm and write M0 themselves, without saving it
+    (csrc/lds_dma.h, dma16).
     That is only sound while hipcc keeps nothing of its own in M0 inside those kernels: check the generated ISA.
     (-DSWEM_ISA_SUBSET: every block tile, the two-plane kernels of both operand formats, the eight-wave and 16-k-block forms --
     a fifth of the instantiations, so that the check compiles in about a minute; the rest: the slow test above.)"""
@@ -96,11 +97,11 @@ def test_lds_dma_kernels_are_the_only_m0_users():
 
 def _check_m0(subset, at_least):
     import subprocess
-    src = os.path.join(os.path.dirname(__file__), '..', 'swem_amd', 'csrc', 'conv.hip')
+    csrc = os.path.join(os.path.dirname(__file__), '..', 'swem_amd', 'csrc')
     asm = ''
-    for unit in ([], ['-DSWEM_CONV_T256_ONLY']):        # (conv.hip is two translation units: swem_amd/build.py)
+    for unit, flags in (('conv_presplit.hip', ['-DSWEM_ISA_SUBSET'] if subset else []), ('conv_t256.hip', [])):   # (the LDS-DMA kernels' units)
         asm += subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S',
-                               *(['-DSWEM_ISA_SUBSET'] if subset else []), *unit, src, '-o', '-'], check=True,
+                               *flags, os.path.join(csrc, unit), '-o', '-'], check=True,
                               capture_output=True, text=True, timeout=1800).stdout
     checked = 0
     t256 = 0

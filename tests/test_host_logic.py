@@ -468,10 +468,14 @@ def test_round6_host_logic(tmp_path, monkeypatch):
     ops.FAULT_OWNERS.clear()
     txt = ops._fault_text(ops.FAULT_RANGE | ops.FAULT_KSPLIT)
     assert 'K-split' in txt and 'fp16 range' in txt and 'unknown' not in txt and 'unknown fault bits' in ops._fault_text(64)
-    # --- build: a unit is rebuilt for ITS headers only (conv.hip does not include the training header)
-    conv_h = {p.split('/')[-1] for p in build._headers_of(build.CSRC + '/conv.hip')}
+    # --- build: a unit is rebuilt for ITS headers only (no convolution unit includes the training header)
+    conv_units = [s for s in build.SOURCES if s.startswith('conv')]
+    assert sorted(conv_units) == ['conv.hip', 'conv_f32.hip', 'conv_presplit.hip', 'conv_t256.hip']
+    for unit in conv_units:
+        conv_h = {p.split('/')[-1] for p in build._headers_of(build.CSRC + '/' + unit)}
+        assert 'swem_hip.h' in conv_h and 'conv_common.h' in conv_h and 'swem_hip_train.h' not in conv_h, unit
     train_h = {p.split('/')[-1] for p in build._headers_of(build.CSRC + '/train.hip')}
-    assert 'swem_hip.h' in conv_h and 'swem_hip_train.h' not in conv_h and 'swem_hip_train.h' in train_h
+    assert 'swem_hip_train.h' in train_h
     # --- the one-rank process-group switch
     monkeypatch.delenv('SWEM_DIST_SINGLE_RANK', raising=False)
     assert not sdist.single_rank_group() and not sdist.active()

@@ -20,22 +20,16 @@ def build():
     objs = []
     for name in ('api', 'pointwise', 'train', 'train_conv', 'match'):
         objs.append(os.path.join(csrc, name + '.o'))
-    for name in ('em', 'conv', 'bneck'):
+    for name in ('em', 'conv', 'conv_f32', 'conv_presplit', 'conv_t256', 'bneck'):
         o = '/tmp/%s_stamps.o' % name
         subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC',
                                '-DSWEM_EM_STAMPS', '-DSWEM_STAMP_BLOCK=%d' % int(os.environ.get('SWEM_STAMP_BLOCK', '0')),
                                *(['-DSWEM_PROLOGUE_STAMPS'] if os.environ.get('SWEM_PROLOGUE_STAMPS') else []),
-                               # (SWEM_STAMPS_SUBSET=1: a fifth of conv.hip's instantiations -- every tile, two-plane kernels,
-                               # variants 0 / 1 / 4 / 6 / 8 -- builds in a minute instead of five)
-                               *(['-DSWEM_ISA_SUBSET'] if name == 'conv' and os.environ.get('SWEM_STAMPS_SUBSET') else []),
+                               # (SWEM_STAMPS_SUBSET=1: a fifth of conv_presplit.hip's instantiations -- every tile, two-plane
+                               # kernels, variants 0 / 1 / 4 / 6 / 8 -- builds in a minute instead of five)
+                               *(['-DSWEM_ISA_SUBSET'] if name == 'conv_presplit' and os.environ.get('SWEM_STAMPS_SUBSET') else []),
                                '-c', os.path.join(csrc, name + '.hip'), '-o', o])
         objs.append(o)
-        if name == 'conv':          # (its second unit: conv_t256_kernel alone)
-            o2 = '/tmp/conv_t256_stamps.o'
-            subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-DSWEM_EM_STAMPS',
-                                   '-DSWEM_STAMP_BLOCK=%d' % int(os.environ.get('SWEM_STAMP_BLOCK', '0')), '-DSWEM_CONV_T256_ONLY',
-                                   '-c', os.path.join(csrc, 'conv.hip'), '-o', o2])
-            objs.append(o2)
     subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-shared', '-fPIC', '-o', out] + objs)
     return out
 

@@ -7,7 +7,8 @@ import json
 import os
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
-SOURCES = ('swem_amd/csrc/conv.hip', 'swem_amd/csrc/lds_dma.h', 'swem_amd/csrc/bf16_split.h', 'swem_amd/csrc/common.h',
+SOURCES = ('swem_amd/csrc/conv.hip', 'swem_amd/csrc/conv_f32.hip', 'swem_amd/csrc/conv_presplit.hip', 'swem_amd/csrc/conv_t256.hip',
+           'swem_amd/csrc/conv_common.h', 'swem_amd/csrc/conv_mma16.h', 'swem_amd/csrc/lds_dma.h', 'swem_amd/csrc/bf16_split.h', 'swem_amd/csrc/common.h',
            'include/swem_hip.h')
 
 

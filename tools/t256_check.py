@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The 256x256-tile f16x3 kernel (conv.hip, conv_t256_kernel; plan tile 4 x 4) against the 128x128 kernel (variant 6) and fp64.
+"""The 256x256-tile f16x3 kernel (conv_t256.hip, conv_t256_kernel; plan tile 4 x 4) against the 128x128 kernel (variant 6) and fp64.
     python tools/t256_check.py
 Same k order and products: without K-split the outputs must be IDENTICAL; with K-split equal to 1e-6 of the output scale."""
 import os

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of conv_t256_kernel's epilogue (round 6: accumulators staged through the LDS, ONE out_tile32 in a loop -- conv.hip,
+# A/B of conv_t256_kernel's epilogue (round 6: accumulators staged through the LDS, ONE out_tile32 in a loop -- conv_t256.hip,
 # t256_epilogue) against the round-5 form (conv_epilogue16: twelve unrolled copies, 68 spilled registers), layer by layer and in
 # the frame.  swem_amd/libswem_hip_oldepi.so = this tree with the two call sites switched back (built by hand beside the library).
 # Output: gpurun_out/t256_epilogue_ab.txt
