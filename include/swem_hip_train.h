@@ -43,6 +43,37 @@ int swem_vos_loss_frame_bwd_f32(void *stream, const float *prob, const float *ra
                                 int N1, int T, long long HW, long long k, const long long *k_dev, float aux_ratio,
                                 const float *gout);
 
+/* ------------------------------------------------------------------------------------
+ * LOSS.AUX = 'lovasz' (losses/__init__.py:11, 27-28, 45-56 with lovasz_losses.py:155-220 at its defaults classes='present',
+ * per_image=True): the Lovasz-softmax loss in the place of the mask-IoU loss.  Runs frame by frame behind
+ * swem_vos_loss_frame_fwd_f32 on the `prob` planes that call wrote; same label / valid conventions as above.
+ * Per clip b and valid channel c (rank r among the valid channels):  fg = (label == r),  e = |fg - prob|,  G = sum fg.  A channel
+ * with G = 0 in the frame ("absent") and an invalid channel are skipped.  The errors are sorted in DESCENDING order, TIES BY
+ * ASCENDING PIXEL (a stable sort: the reference's torch.sort leaves ties in no defined order, lovasz_losses.py:197); with cf
+ * foreground pixels before position k and U = G + (k - cf), the weight of position k is
+ *   g = 1 / U (foreground pixel),  (G - cf) / (U (U + 1)) (background pixel)
+ * -- lovasz_grad's differenced Jaccard index (lovasz_losses.py:19-31) in closed form on integer counts -- and the channel's loss
+ * is sum_k e_sorted[k] g[k] (:200), summed in fp64 in a fixed order.
+ *   glov  [B][N1][HW]   g at each PIXEL's place (0 on skipped channels); may be NULL (the backward needs it)
+ *   lov   [B][N1][2]    {channel loss, G} (both 0 on skipped channels)
+ *   keys_out, payload_out [B][N1][HW] (each may be NULL; for tests): the sorted order -- bits of e, and pixel | fg << 31; the
+ *                       rows of skipped channels are not written
+ * Workspace contents on entry are irrelevant.  HW < 2^31, N1 <= 8 and B*N1 <= 65535, else refused before any launch. */
+size_t swem_lovasz_workspace(int B, int N1, long long HW);
+int swem_lovasz_frame_fwd_f32(void *stream, const float *prob, const long long *label, long long label_bs,
+                              const float *valid, float *glov, float *lov, unsigned *keys_out, unsigned *payload_out, int B,
+                              int N1, long long HW, void *ws, size_t ws_bytes);
+/* losses = {total, main, aux} (losses/__init__.py:56-60): main from rowstat [T][B][4] as swem_vos_loss_reduce_f32, aux from
+ * lov [T][B][N1][2] -- mean over the frame's present channels (lovasz_losses.py:201; 0 without one), over frames (:166), over clips */
+int swem_lovasz_reduce_f32(void *stream, const float *rowstat, const float *lov, float *losses, int B, int N1, int T,
+                           long long HW, long long k, const long long *k_dev, float aux_ratio);
+/* d total_loss / d logits of one frame, times gout[0] (NULL = 1): the cross-entropy half as swem_vos_loss_frame_bwd_f32, the
+ * Lovasz half d e / d p = sign(p - fg) (0 at 0, as torch.abs) times glov, through the softmax over the valid channels */
+int swem_lovasz_frame_bwd_f32(void *stream, const float *prob, const float *raw, const long long *label, long long label_bs,
+                              const float *valid, const float *rowstat, const float *lov, const float *glov, float *dlogits,
+                              int B, int N1, int T, long long HW, long long k, const long long *k_dev, float aux_ratio,
+                              const float *gout);
+
 /* torch.optim.AdamW, one step over a flat parameter buffer (solver/solver.py:38-41):
  *   p *= 1 - lr*wd;  m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g*g;  p -= lr/(1-b1^step) * m / (sqrt(v)/sqrt(1-b2^step) + eps) */
 int swem_adamw_f32(void *stream, float *p, const float *g, float *m, float *v, long long n, float lr, float beta1,

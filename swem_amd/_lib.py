@@ -82,6 +82,10 @@ SIGNATURES = {
     'swem_vos_loss_frame_fwd_f32': (_i, [_p, _p, _p, _ll, _p, _p, _p, _p, _p, _i, _i, _ll, _ll, _p, _p, _sz]),
     'swem_vos_loss_reduce_f32': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _ll, _ll, _p, _f]),
     'swem_vos_loss_frame_bwd_f32': (_i, [_p, _p, _p, _p, _ll, _p, _p, _p, _p, _i, _i, _i, _ll, _ll, _p, _f, _p]),
+    'swem_lovasz_workspace': (_sz, [_i, _i, _ll]),
+    'swem_lovasz_frame_fwd_f32': (_i, [_p, _p, _p, _ll, _p, _p, _p, _p, _p, _i, _i, _ll, _p, _sz]),
+    'swem_lovasz_reduce_f32': (_i, [_p, _p, _p, _p, _i, _i, _i, _ll, _ll, _p, _f]),
+    'swem_lovasz_frame_bwd_f32': (_i, [_p, _p, _p, _p, _ll, _p, _p, _p, _p, _p, _i, _i, _i, _ll, _ll, _p, _f, _p]),
     'swem_adamw_f32': (_i, [_p, _p, _p, _p, _p, _ll, _f, _f, _f, _f, _f, _i]),
     'swem_adamw_gated_f32': (_i, [_p, _p, _p, _p, _p, _ll, _f, _f, _f, _f, _f, _i, _p, _i, _p]),
     'swem_fault_flags_f32': (_i, [_p, _p, _p]),

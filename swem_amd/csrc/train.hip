@@ -5,28 +5,15 @@
 
 #include "../../include/swem_hip_train.h"
 #include "common.h"
+#include "loss_common.h"
 #include "bf16_split.h"
 
 namespace {
-
-constexpr int LOSS_MAXC = 8;  // objects + background per clip (reference trains with MAX_NUM_OBJS = 2)
 
 // order-preserving map float -> uint (ascending)
 __device__ __forceinline__ unsigned fkey(float x) {
   unsigned u = __float_as_uint(x);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-  const int tid = threadIdx.x;
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  __syncthreads();
-  if ((tid & 63) == 0) sh[tid >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (tid == 0)
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-  return t;  // valid in thread 0
 }
 
 // bce_losses.py:28-36 / losses/__init__.py:50-55: softmax over the valid channels, per-pixel CE, partial IoU sums

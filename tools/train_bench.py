@@ -2,6 +2,7 @@
 """Times SWEMTrainer.one_step (reference swem_trainer.py:59-108) on the reference's training shapes
 (configs/config.py: 3 frames of 384x384 per clip, MAX_NUM_OBJS = 2, ResNet-50, K = 256, 4 EM iterations).
    python tools/train_bench.py [--clips 4] [--steps 5] [--warmup 2] [--size 384] [--objects 2] [--amp] [--no-autotune]
+                               [--aux {iou,lovasz,none}]
 Data parallel (BASELINE configs C / D: batch 32 = 4 clips on each of 8 GPUs): one process per GPU under torchrun,
    python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 tools/train_bench.py --clips 4
 every rank steps its own clips, the flat gradient buffer is all-reduced over RCCL before the optimizer step
@@ -34,6 +35,7 @@ def main():
     ap.add_argument('--cpu-baseline', action='store_true', help='time the oracle\'s training step (CPU) on one clip beside it')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--amp', action='store_true', help='config.AMP: bf16-operand convolutions')
+    ap.add_argument('--aux', choices=['iou', 'lovasz', 'none'], default='iou', help='LOSS.AUX (configs/config.py:82)')
     ap.add_argument('--per-step', action='store_true', help='synchronise and print every step time (stderr)')
     ap.add_argument('--save-plans', default=None)
     ap.add_argument('--load-plans', default=None, help='reuse tuned conv plans (profiler runs)')
@@ -60,7 +62,8 @@ def main():
     ops.AUTOTUNE = not a.no_autotune and not a.load_plans
     tr = SWEMTrainer(dict(SOLVER=dict(STAGE=0, BASE_LR=2e-5, PRETRAIN_ITERS=[150000, 300000], GAMMA=0.1,
                                       OPTIMIZER='AdamW', WEIGHT_DECAY=5e-4),
-                          LOSS=dict(NAME='boots_ce', BS_RATIO=0.3, BS_PERIOD=[20000, 70000], AUX='iou', AUX_RATIO=1.0),
+                          LOSS=dict(NAME='boots_ce', BS_RATIO=0.3, BS_PERIOD=[20000, 70000], AUX=None if a.aux == 'none' else a.aux,
+                                    AUX_RATIO=1.0),
                           AMP=a.amp), model, lanes=a.lanes)
     if a.load_plans:
         tr.book.load(a.load_plans)
@@ -171,7 +174,7 @@ def main():
         line = {'metric': 'training clips/s (3 x %dx%d frames, %d objects, %s, %s)' % (
             a.size, a.size, a.objects, a.backbone, 'AMP: bf16 conv operands' if a.amp else 'fp32-accurate'), 'value': a.clips / dt,
             'unit': 'clips/s', 'ms_per_step': dt * 1e3, 'clips_per_step': a.clips,
-            'total_loss': float(losses['total_loss']), 'graph': tr._graph is not None, 'lanes': tr.lanes,
+            'total_loss': float(losses['total_loss']), **({} if a.aux == 'iou' else {'aux': a.aux}), 'graph': tr._graph is not None, 'lanes': tr.lanes,
             'clips_per_lane': [b1 - b0 for b0, b1 in tr._lane_state['chunks']], 'n_gpus': world,
             ('rccl_ranks' if (torch.distributed.is_initialized() and torch.distributed.get_backend() == 'nccl') else 'ranks'):
                 torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1,
