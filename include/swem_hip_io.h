@@ -84,6 +84,38 @@ size_t swem_png_workspace(int T, int H, int W);
 int swem_png_encode_u8(void *stream, const unsigned char *maps, const unsigned char *palette768, unsigned char *blob,
                        size_t blob_bytes, long long *offsets, int T, int H, int W, void *ws, size_t ws_bytes);
 
+/* The same files with a Huffman table of each segment's own, and truecolour pictures: the overlay pictures of
+ * utils/visualization.py:46-72 as basic_evaluator.py:185-196, 241-265 writes them.
+ *   channels 1 : index maps as above (filter type 0; colour type 3 with a palette, 0 without)
+ *   channels 3 : [T][H][W][3] uint8 RGB -> colour type 2, no PLTE.  Every scanline takes the filter type 0-4 with the smallest
+ *                sum of |signed residual| (ties: the lower type); the row above the first row of a segment is the source
+ *                picture's, above row 0 zeros.
+ * A scanline is rw = channels * W + 1 bytes; a segment is min(16, floor(65535 / rw)) whole scanlines, coded on its own with
+ * literals and matches at distance 1 and ended as above, so one-channel files under SWEM_PNG_CODES_FIXED are byte for byte
+ * those of swem_png_encode_u8.
+ *   SWEM_PNG_CODES_FIXED   : a segment is the smaller of its stored block and its fixed-code block (coded only if strictly
+ *                            smaller)
+ *   SWEM_PNG_CODES_DYNAMIC : also a dynamic block (RFC 1951 section 3.2.7): literal/length code lengths of at most 15 bits,
+ *                            optimal for the segment's own histogram (package-merge, ties by symbol index), canonical codes,
+ *                            the lengths run-length coded with symbols 16-18 under a code-length code of at most 7 bits, and
+ *                            one distance code of length 1 (HDIST = 0: only distance 1 occurs).  The segment takes the
+ *                            dynamic block only if strictly smaller than the fixed one, and a coded block only if strictly
+ *                            smaller than the stored one: a file never grows past the capacity.
+ * Capacity: the formula above with rw = channels * W + 1 in the place of W + 1, without the 780 PLTE bytes for 3 channels.
+ * 0 for a shape the encoder refuses (channels not 1 or 3, H < 1, W < 1, channels * W + 1 > 65535). */
+#define SWEM_PNG_CODES_FIXED 0
+#define SWEM_PNG_CODES_DYNAMIC 1
+size_t swem_png_capacity_px(int H, int W, int channels);
+size_t swem_png_workspace_px(int T, int H, int W, int channels);
+/* pixels: [T][H][W] (channels 1) or [T][H][W][3] (channels 3) uint8 (device); palette768 as above, NULL with 3 channels;
+ * blob_bytes >= T * swem_png_capacity_px(H, W, channels); offsets, ws (swem_png_workspace_px bytes) as above.  Refused before
+ * anything is launched: null pointers, channels not 1 or 3, a palette with 3 channels, an unknown `codes`, a row past 65535
+ * bytes, a short blob or workspace.  Three launches; the encode launch declares up to 65536 bytes of LDS for the segment and,
+ * under SWEM_PNG_CODES_DYNAMIC, about 10 KiB of tables behind it. */
+int swem_png_encode_px_u8(void *stream, const unsigned char *pixels, int channels, const unsigned char *palette768, int codes,
+                          unsigned char *blob, size_t blob_bytes, long long *offsets, int T, int H, int W, void *ws,
+                          size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,10 @@
 //                       the bits are OR-ed into the segment's zeroed slot of the workspace.  A segment that would not shrink is a
 //                       stored block.  Every segment ends on a byte boundary (an empty stored block after the coded one), so
 //                       that segments are joined by copying bytes.  Also the segment's Adler-32 sums.
-//   png_offsets_kernel  file sizes from the segment lengths, prefix-summed into offsets[T + 1]
+//   png_encode_px_kernel  the second form (swem_png_encode_px_u8): 1 or 3 channels -- truecolour
+//                       scanlines under a filter type of their own --, and with dynamic codes a Huffman table per segment
+//                       (histogram in LDS, lengths, codes and block header by lane 0), taken where it is the smallest form
+//   png_offsets_kernel file sizes from the segment lengths, prefix-summed into offsets[T + 1]
 //   png_pack_kernel     one wavefront per chunk: copies a segment's bytes to its place in the blob as an IDAT chunk with its
 //                       CRC-32 (every lane runs the table over a piece, the registers are joined with x^(8n) mod P); the last
 //                       wavefront of a frame writes the signature, IHDR, PLTE, the closing IDAT (final empty block and the
@@ -36,9 +39,9 @@ struct PngLayout {
   size_t slot;          // bytes of a segment's slot in the workspace (its stored form, rounded up to words)
 };
 
-inline PngLayout png_layout(int H, int W) {
+inline PngLayout png_layout(int H, int row_bytes) {
   PngLayout L;
-  L.rw = W + 1;
+  L.rw = row_bytes + 1;
   L.rows = PNG_SEG_MAX / L.rw < PNG_SEG_ROWS ? PNG_SEG_MAX / L.rw : PNG_SEG_ROWS;
   L.nseg = (H + L.rows - 1) / L.rows;
   L.slot = align_up((size_t)L.rows * L.rw + PNG_STORED_EXTRA, 16);
@@ -94,6 +97,164 @@ __global__ __launch_bounds__(64) void png_encode_kernel(const unsigned char *__r
     }
     png_tokens(seg, p0, p1, bits);
     bits.close();
+    if (lane == 0) {
+      png_or_byte(words, coded - 2u, 0xffu);
+      png_or_byte(words, coded - 1u, 0xffu);
+    }
+  } else {
+    len = stored;
+    if (lane == 0) {
+      out[0] = 0;                                     // BFINAL 0, BTYPE 00
+      out[1] = (unsigned char)n;
+      out[2] = (unsigned char)(n >> 8);
+      out[3] = (unsigned char)~n;
+      out[4] = (unsigned char)(~n >> 8);
+    }
+    for (int i = lane; i < n; i += 64) out[PNG_STORED_EXTRA + i] = seg[i];
+  }
+
+  unsigned long long a, w;
+  png_adler_piece(seg + p0, p1 - p0, &a, &w);
+  w += a * (unsigned long long)(n - p1);              // < 2^8 * 2^10 * 2^16
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_xor(a, off);
+    w += __shfl_xor(w, off);
+  }
+  if (lane == 0) meta[t * nseg + s] = make_uint4(len, (unsigned)(a % PNG_ADLER_MOD), (unsigned)(w % PNG_ADLER_MOD), 0u);
+}
+
+// what the dynamic form keeps in LDS behind the segment
+struct PngDynLds {
+  uint32_t freq[288];                   // the segment's literal/length histogram
+  uint32_t hdr[PNG_HDR_WORDS];          // the block header, from bit 0
+  uint32_t hdr_bits;
+  uint16_t code[288];
+  unsigned char len[288];
+  PngBuildScratch S;
+};
+
+// The second form: `channels` 1 (filter type 0, as above) or 3 (every scanline under the filter type 0-4 of the smallest sum of
+// |signed residual|; the row above comes from the source picture, zeros above row 0), and with `dynamic` a Huffman table of the
+// segment's own.  The lanes histogram their pieces into LDS; the used symbols are ranked by all lanes; lane 0 builds the
+// lengths (package-merge, at most 15 bits), the codes and the block header; every lane then counts its piece under the fixed
+// and the dynamic code at once and two prefix sums give the two coded sizes.  Dynamic only if strictly smaller than fixed; a
+// coded form only if strictly smaller than stored.  Slots, meta and the closing empty stored block are those of the kernel above.
+__global__ __launch_bounds__(64) void png_encode_px_kernel(const unsigned char *__restrict__ pixels, unsigned char *__restrict__ slots,
+                                                           uint4 *__restrict__ meta, int H, int W, int channels, int dynamic,
+                                                           int seg_rows, size_t slot_bytes) {
+  extern __shared__ __align__(16) unsigned char seg[];
+  const int lane = threadIdx.x;
+  const int nseg = gridDim.x;
+  const size_t t = blockIdx.y, s = blockIdx.x;
+  const int row0 = (int)s * seg_rows;
+  const int rows = H - row0 < seg_rows ? H - row0 : seg_rows;
+  const int rb = channels * W, rw = rb + 1;
+  const int n = rows * rw;                           // 1 < n <= 65535
+  PngDynLds *D = reinterpret_cast<PngDynLds *>(seg + (((size_t)seg_rows * rw + 15) & ~(size_t)15));   // (only with `dynamic`)
+  const unsigned char *src = pixels + (t * H + row0) * rb;
+  for (int r = 0; r < rows; ++r) {
+    const unsigned char *cur = src + (size_t)r * rb;
+    int type = 0;
+    if (channels == 3) {
+      const unsigned char *up = row0 + r > 0 ? cur - rb : nullptr;
+      PngFilterSums sums = {{0u, 0u, 0u, 0u, 0u}};
+      png_filter_sums(cur, up, lane, 64, rb, 3, &sums);
+#pragma unroll
+      for (int k = 0; k < 5; ++k)
+        for (int off = 32; off > 0; off >>= 1) sums.s[k] += __shfl_xor(sums.s[k], off);
+      type = png_filter_choice(sums);
+      png_filter_row(type, cur, up, lane, 64, rb, 3, seg + r * rw);
+    } else {
+      for (int x = lane; x < W; x += 64) seg[r * rw + 1 + x] = cur[x];
+    }
+    if (lane == 0) seg[r * rw] = (unsigned char)type;
+  }
+  if (dynamic) {
+    for (int k = lane; k < 288; k += 64) {
+      D->freq[k] = 0u;
+      D->len[k] = 0;
+    }
+    for (int k = lane; k < PNG_HDR_WORDS; k += 64) D->hdr[k] = 0u;
+  }
+  __syncthreads();
+
+  const int piece = (n + 63) / 64;
+  const int p0 = lane * piece < n ? lane * piece : n;
+  const int p1 = p0 + piece < n ? p0 + piece : n;
+  unsigned mine_f, mine_d = 0u, eob_d = 0u;
+  if (dynamic) {
+    PngHistSink hist = {D->freq};
+    png_symbols(seg, p0, p1, hist);
+    if (lane == 0) png_count_one(D->freq + PNG_EOB);
+    __syncthreads();
+    int used = 0;
+    for (int i = lane; i < PNG_NSYM; i += 64)
+      if (D->freq[i]) {
+        D->S.order[png_rank(D->freq, PNG_NSYM, i)] = (uint16_t)i;
+        ++used;
+      }
+    for (int off = 32; off > 0; off >>= 1) used += __shfl_xor(used, off);
+    __syncthreads();
+    if (lane == 0) {
+      png_lengths_sorted(D->freq, D->S.order, used, PNG_MAXBITS, D->len, &D->S);
+      png_canonical(D->len, PNG_NSYM, D->code, &D->S);
+      D->hdr_bits = png_dynamic_header(D->len, D->hdr, &D->S);
+    }
+    __syncthreads();
+    PngFixedCountSink cf = {0u};
+    PngLenCountSink cd = {D->len, 1u, 0u};
+    PngBothSinks<PngFixedCountSink, PngLenCountSink> both = {cf, cd};
+    png_symbols(seg, p0, p1, both);
+    mine_f = cf.bits;
+    mine_d = cd.bits + (lane == 0 ? D->hdr_bits : 0u);
+    eob_d = D->len[PNG_EOB];
+  } else {
+    PngCountSink cnt = {0u};
+    png_tokens(seg, p0, p1, cnt);
+    mine_f = cnt.bits;
+  }
+  mine_f += lane == 0 ? 3u : 0u;                      // the block header goes first
+  unsigned incl_f = mine_f, incl_d = mine_d;
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned vf = __shfl_up(incl_f, d), vd = __shfl_up(incl_d, d);
+    if (lane >= d) {
+      incl_f += vf;
+      incl_d += vd;
+    }
+  }
+  // header and tokens, the end-of-block code, an empty stored block: 3 zero bits, padding, 00 00 FF FF
+  const unsigned coded_f = (__shfl(incl_f, 63) + 7u + 3u + 7u) / 8u + 4u;
+  const unsigned coded_d = (__shfl(incl_d, 63) + eob_d + 3u + 7u) / 8u + 4u;
+  const bool use_d = dynamic && coded_d < coded_f;
+  const unsigned coded = use_d ? coded_d : coded_f;
+  const unsigned stored = (unsigned)n + PNG_STORED_EXTRA;
+  unsigned char *out = slots + (t * nseg + s) * slot_bytes;
+  unsigned len;
+  if (coded < stored) {
+    len = coded;
+    uint32_t *words = reinterpret_cast<uint32_t *>(out);
+    for (unsigned w = lane; w < (coded + 3u) / 4u; w += 64) words[w] = 0u;     // (coded + 3) / 4 * 4 <= slot_bytes
+    __threadfence();                                  // the zeros are in place before any lane ORs into them
+    __syncthreads();
+    if (use_d) {
+      for (unsigned w = lane; w < (D->hdr_bits + 31u) / 32u; w += 64) png_or_word(words + w, D->hdr[w]);
+      PngCodeSink bits;
+      bits.code = D->code;
+      bits.len = D->len;
+      bits.out.open(words, incl_d - mine_d + (lane == 0 ? D->hdr_bits : 0u));
+      png_symbols(seg, p0, p1, bits);
+      if (lane == 63) bits.literal(PNG_EOB);          // (its piece is the last, or empty at the end)
+      bits.out.close();
+    } else {
+      PngBitSink bits;
+      bits.open(words, incl_f - mine_f);
+      if (lane == 0) {
+        const PngTok fixed_block = {2u, 3};           // BFINAL 0, BTYPE 01
+        bits.put(fixed_block);
+      }
+      png_tokens(seg, p0, p1, bits);
+      bits.close();
+    }
     if (lane == 0) {
       png_or_byte(words, coded - 2u, 0xffu);
       png_or_byte(words, coded - 1u, 0xffu);
@@ -189,8 +350,8 @@ __device__ __forceinline__ void png_wave_chunk(const uint32_t *tab, unsigned cha
 // of the file.
 __global__ __launch_bounds__(64) void png_pack_kernel(const unsigned char *__restrict__ slots, const uint4 *__restrict__ meta,
                                                       const long long *__restrict__ offsets, unsigned char *__restrict__ blob,
-                                                      const PngPalette pal, int has_palette, int H, int W, int seg_rows,
-                                                      size_t slot_bytes) {
+                                                      const PngPalette pal, int has_palette, int H, int W, int channels,
+                                                      int seg_rows, size_t slot_bytes) {
   __shared__ uint32_t tab[256];
   __shared__ unsigned char small[768];
   const int lane = threadIdx.x;
@@ -219,7 +380,7 @@ __global__ __launch_bounds__(64) void png_pack_kernel(const unsigned char *__res
     png_be32(small, (uint32_t)W);
     png_be32(small + 4, (uint32_t)H);
     small[8] = 8;                                     // bit depth
-    small[9] = has_palette ? 3 : 0;                   // colour type: palette / grayscale
+    small[9] = channels == 3 ? 2 : (has_palette ? 3 : 0);      // colour type: truecolour / palette / grayscale
     small[10] = small[11] = small[12] = 0;            // compression, filter method, no interlace
   }
   __syncthreads();
@@ -238,7 +399,7 @@ __global__ __launch_bounds__(64) void png_pack_kernel(const unsigned char *__res
     for (int k = 0; k < nseg; ++k) {
       const uint4 m = meta[t * nseg + k];
       const int row0 = k * seg_rows;
-      const unsigned long long n = (unsigned long long)(H - row0 < seg_rows ? H - row0 : seg_rows) * (unsigned)(W + 1);
+      const unsigned long long n = (unsigned long long)(H - row0 < seg_rows ? H - row0 : seg_rows) * (unsigned)(channels * W + 1);
       B = (B + n * A + m.z) % PNG_ADLER_MOD;
       A = (A + m.y) % PNG_ADLER_MOD;
     }
@@ -301,7 +462,67 @@ extern "C" int swem_png_encode_u8(void *stream, const unsigned char *maps, const
                      PNG_FIXED_HEAD + (has_palette ? PNG_PLTE_BYTES : 0));
   SWEM_CHECK_LAUNCH("png_offsets");
   hipLaunchKernelGGL(png_pack_kernel, dim3((unsigned)L.nseg + 1u, (unsigned)T), dim3(64), 0, ST, slots, meta, offsets, blob, pal,
-                     has_palette, H, W, L.rows, L.slot);
+                     has_palette, H, W, 1, L.rows, L.slot);
+  SWEM_CHECK_LAUNCH("png_pack");
+  return SWEM_OK;
+}
+
+namespace {
+inline bool png_shape_ok_px(int H, int W, int channels) {
+  return (channels == 1 || channels == 3) && H >= 1 && W >= 1 && (long long)channels * W + 1 <= PNG_SEG_MAX;
+}
+}  // namespace
+
+extern "C" size_t swem_png_capacity_px(int H, int W, int channels) {
+  if (!png_shape_ok_px(H, W, channels)) return 0;
+  const PngLayout L = png_layout(H, channels * W);
+  return (size_t)PNG_FIXED_HEAD + (channels == 1 ? PNG_PLTE_BYTES : 0) + 2 + (size_t)H * L.rw +
+         (size_t)L.nseg * (PNG_STORED_EXTRA + PNG_CHUNK_EXTRA) + PNG_TAIL_BYTES;
+}
+
+extern "C" size_t swem_png_workspace_px(int T, int H, int W, int channels) {
+  if (T < 1 || !png_shape_ok_px(H, W, channels)) return 0;
+  const PngLayout L = png_layout(H, channels * W);
+  return (size_t)T * L.nseg * (sizeof(uint4) + L.slot);
+}
+
+extern "C" int swem_png_encode_px_u8(void *stream, const unsigned char *pixels, int channels, const unsigned char *palette768,
+                                     int codes, unsigned char *blob, size_t blob_bytes, long long *offsets, int T, int H, int W,
+                                     void *ws, size_t ws_bytes) {
+  SWEM_REQUIRE(pixels && blob && offsets && ws, SWEM_E_ARG, "png_encode_px: null pointer");
+  SWEM_REQUIRE(png_aligned(ws, 16) && png_aligned(offsets, 8), SWEM_E_ARG,
+               "png_encode_px: ws must be 16-byte aligned, offsets 8-byte aligned");
+  SWEM_REQUIRE(channels == 1 || channels == 3, SWEM_E_ARG, "png_encode_px: channels is 1 or 3, got %d", channels);
+  SWEM_REQUIRE(channels == 1 || !palette768, SWEM_E_ARG, "png_encode_px: a truecolour picture takes no palette");
+  SWEM_REQUIRE(codes == SWEM_PNG_CODES_FIXED || codes == SWEM_PNG_CODES_DYNAMIC, SWEM_E_ARG,
+               "png_encode_px: codes is SWEM_PNG_CODES_FIXED or SWEM_PNG_CODES_DYNAMIC, got %d", codes);
+  SWEM_REQUIRE(png_shape_ok_px(H, W, channels), SWEM_E_SHAPE,
+               "png_encode_px: need H >= 1, W >= 1 and channels * W + 1 <= 65535, got %dx%d with %d channels", H, W, channels);
+  SWEM_REQUIRE(T >= 1 && T <= 65535, SWEM_E_SHAPE, "png_encode_px: need 1 <= T <= 65535 frames, got %d", T);
+  const PngLayout L = png_layout(H, channels * W);
+  SWEM_REQUIRE(L.nseg < 0x7fffffff, SWEM_E_SHAPE, "png_encode_px: %d segments exceed one launch", L.nseg);
+  const size_t cap = swem_png_capacity_px(H, W, channels), need = swem_png_workspace_px(T, H, W, channels);
+  SWEM_REQUIRE(blob_bytes >= (size_t)T * cap, SWEM_E_WORKSPACE,
+               "png_encode_px: insufficient workspace: blob %zu < %zu bytes (T * swem_png_capacity_px)", blob_bytes, (size_t)T * cap);
+  SWEM_REQUIRE(ws_bytes >= need, SWEM_E_WORKSPACE, "png_encode_px: insufficient workspace: %zu < %zu bytes", ws_bytes, need);
+  uint4 *meta = static_cast<uint4 *>(ws);
+  unsigned char *slots = static_cast<unsigned char *>(ws) + (size_t)T * L.nseg * sizeof(uint4);
+  PngPalette pal;
+  __builtin_memset(pal.rgb, 0, 768);
+  if (palette768) __builtin_memcpy(pal.rgb, palette768, 768);
+  const int has_palette = palette768 ? 1 : 0;
+  const int dynamic = codes == SWEM_PNG_CODES_DYNAMIC ? 1 : 0;
+  // the segment (<= 65536 bytes) and, behind it, the tables of the dynamic form: past 64 KiB for the longest rows
+  const size_t lds = align_up((size_t)L.rows * L.rw, 16) + (dynamic ? sizeof(PngDynLds) : 0);
+  SWEM_ALLOW_LDS(png_encode_px_kernel, 65536 + sizeof(PngDynLds));
+  hipLaunchKernelGGL(png_encode_px_kernel, dim3((unsigned)L.nseg, (unsigned)T), dim3(64), lds, ST, pixels, slots, meta, H, W,
+                     channels, dynamic, L.rows, L.slot);
+  SWEM_CHECK_LAUNCH("png_encode_px");
+  hipLaunchKernelGGL(png_offsets_kernel, dim3(1), dim3(256), 0, ST, meta, offsets, T, L.nseg,
+                     PNG_FIXED_HEAD + (has_palette ? PNG_PLTE_BYTES : 0));
+  SWEM_CHECK_LAUNCH("png_offsets");
+  hipLaunchKernelGGL(png_pack_kernel, dim3((unsigned)L.nseg + 1u, (unsigned)T), dim3(64), 0, ST, slots, meta, offsets, blob, pal,
+                     has_palette, H, W, channels, L.rows, L.slot);
   SWEM_CHECK_LAUNCH("png_pack");
   return SWEM_OK;
 }

@@ -12,7 +12,8 @@ utils/visualization.py:40-43).
 * ``IndexMapWriter`` also maps indices to object ids (basic_evaluator.py:202-206) and writes the overlay pictures of
   VAL.VISUALIZE (utils/visualization.py:46-72, basic_evaluator.py:185-196, 241-265), both on the device.
 * ``IndexMapWriter(encode='device')`` encodes the palette PNGs on the device too (csrc/png.hip): the bytes
-  that cross to the host are the files' bytes, and the thread pool only writes them out.
+  that cross to the host are the files' bytes, and the thread pool only writes them out.  ``codes='dynamic'`` gives every segment
+  a Huffman table of its own; ``overlay_encode='device'`` encodes the overlay pictures there as well (truecolour).
 Nothing here touches the model.
 """
 import os
@@ -194,22 +195,36 @@ def default_palette(n=256):
     return pal.flatten().tolist()
 
 
-def png_capacity(H, W):
-    """swem_png_capacity (include/swem_hip_io.h): the largest PNG file `ops.png_encode_u8` writes for an H x W map -- every
-    segment stored, plus the headers.  0 for a shape the encoder refuses."""
+def png_capacity(H, W, channels=1):
+    """swem_png_capacity / swem_png_capacity_px (include/swem_hip_io.h): the largest PNG file `ops.png_encode_u8` writes for an
+    H x W map (channels=1) or an H x W x 3 picture (channels=3) -- every segment stored, plus the headers.  0 for a shape the
+    encoder refuses."""
     from . import _lib
-    return int(_lib.query('swem_png_capacity', int(H), int(W)))
+    if channels == 1:
+        return int(_lib.query('swem_png_capacity', int(H), int(W)))
+    return int(_lib.query('swem_png_capacity_px', int(H), int(W), int(channels)))
 
 
 class IndexMapWriter:
-    def __init__(self, out_dir, palette=None, workers=4, overlay_alpha=0.4, encode='host'):
+    def __init__(self, out_dir, palette=None, workers=4, overlay_alpha=0.4, encode='host', codes='fixed', overlay_encode='host'):
         """encode='host': the index maps cross to the host as they are and PIL writes them on the thread pool.
         encode='device': `ops.png_encode_u8` makes the files on the device; only their bytes cross, and
-        the pool writes them out unchanged.  The palette is then always written with 256 entries.  Overlay pictures are
-        PIL-encoded either way."""
+        the pool writes them out unchanged.  The palette is then always written with 256 entries.
+        codes='dynamic' (with encode='device'): a Huffman table per segment instead of the fixed codes -- smaller files.
+        overlay_encode='host': the overlay pictures cross as pixels and PIL writes them.  overlay_encode='device': they are
+        encoded on the device as truecolour PNGs (adaptive filters, dynamic tables) right after `ops.overlay_u8`; only file bytes
+        cross."""
         if encode not in ('host', 'device'):
             raise ValueError("IndexMapWriter: encode is 'host' or 'device', got %r" % (encode,))
+        if codes not in ('fixed', 'dynamic'):
+            raise ValueError("IndexMapWriter: codes is 'fixed' or 'dynamic', got %r" % (codes,))
+        if codes == 'dynamic' and encode != 'device':
+            raise ValueError("IndexMapWriter: codes='dynamic' needs encode='device'")
+        if overlay_encode not in ('host', 'device'):
+            raise ValueError("IndexMapWriter: overlay_encode is 'host' or 'device', got %r" % (overlay_encode,))
         self.encode = encode
+        self.codes = codes
+        self.overlay_encode = overlay_encode
         self.out_dir = out_dir
         self.palette = default_palette() if palette is None else palette
         self.overlay_alpha = overlay_alpha
@@ -257,11 +272,15 @@ class IndexMapWriter:
         n = stacked.shape[0]
         u8 = ops.pack_u8(stacked) if id_table is None else ops.pack_u8_lut(stacked, id_table)
         device = self.encode == 'device'
-        tensors, od = ([] if device else [u8]), None
+        tensors, od, overlay_files = ([] if device else [u8]), None, None
         if overlay_frames_u8 is not None:
             od = os.path.join(self.out_dir, 'overlay', seq_name)
             os.makedirs(od, exist_ok=True)
-            tensors.append(self._overlay(overlay_frames_u8[first_index:first_index + n], u8, u8.device))
+            pictures = self._overlay(overlay_frames_u8[first_index:first_index + n], u8, u8.device)
+            if self.overlay_encode == 'device':
+                overlay_files = self._encode(list(range(n)), pictures)
+            else:
+                tensors.append(pictures)
         stems = [('%05d' % (first_index + t)) if names is None else names[first_index + t] for t in range(n)]
         kept = [keep is None or (stems[t] if names is not None else first_index + t) in keep for t in range(n)]
         files = None
@@ -270,29 +289,33 @@ class IndexMapWriter:
         hosts, ev = self._to_host(tensors)
 
         def write():
-            if files is not None:
-                for t, data in zip(files[0], self._files_to_host(*files[1:])):
-                    with open(os.path.join(d, stems[t] + '.png'), 'wb') as f:
-                        f.write(data)
+            for where, enc in ((d, files), (od, overlay_files)):
+                if enc is not None:
+                    for t, data in zip(enc[0], self._files_to_host(*enc[1:])):
+                        with open(os.path.join(where, stems[t] + '.png'), 'wb') as f:
+                            f.write(data)
             ev.synchronize()
             for t in range(n):
                 if kept[t] and not device:
                     save_seg_mask(hosts[0].numpy()[t], os.path.join(d, stems[t] + '.png'), self.palette)
-                if od is not None:
+                if od is not None and overlay_files is None:
                     save_rgb(hosts[-1].numpy()[t], os.path.join(od, stems[t] + '.png'))
             return sum(kept)
         self.pending.append(self.pool.submit(write))
 
     def _encode(self, sel, u8):
-        """The frames `sel` of u8 (n,H,W) as PNG files on the device, and the copy of their offsets under way on the copy stream:
-        (sel, blob, offsets on the host, event).  Nothing here waits."""
+        """The frames `sel` of u8 -- (n,H,W) index maps, or (n,H,W,3) overlay pictures -- as PNG files on the device, and the copy
+        of their offsets under way on the copy stream: (sel, blob, offsets on the host, event).  Nothing here waits."""
         if len(sel) == u8.shape[0]:
             maps = u8
         elif sel == list(range(sel[0], sel[-1] + 1)):
             maps = u8[sel[0]:sel[-1] + 1]
         else:
             maps = torch.stack([u8[t] for t in sel])
-        blob, offsets = ops.png_encode_u8(maps, self._palette768())
+        if u8.dim() == 4:
+            blob, offsets = ops.png_encode_u8(maps, None, codes='dynamic')      # (fixed codes never beat the stored form here)
+        else:
+            blob, offsets = ops.png_encode_u8(maps, self._palette768(), codes=self.codes)
         (offs_host,), ev = self._to_host([offsets])
         blob.record_stream(self.copy_stream)
         return sel, blob, offs_host, ev
@@ -319,7 +342,7 @@ class IndexMapWriter:
         idx, _ = ops.argmax_onehot(mask_onehot.float().contiguous(), want_onehot=False)
         u8 = ops.pack_u8(idx) if id_table is None else ops.pack_u8_lut(idx, id_table)
         if self.encode == 'device':
-            blob, offsets = ops.png_encode_u8(u8, self._palette768())
+            blob, offsets = ops.png_encode_u8(u8, self._palette768(), codes=self.codes)
             with open(os.path.join(d, stem + '.png'), 'wb') as f:
                 f.write(blob[:int(offsets[-1])].cpu().numpy().tobytes())
         else:
@@ -327,7 +350,13 @@ class IndexMapWriter:
         if overlay_frame_u8 is not None:
             od = os.path.join(self.out_dir, 'overlay', seq_name)
             os.makedirs(od, exist_ok=True)
-            save_rgb(self._overlay(overlay_frame_u8[None], u8, u8.device).cpu().numpy()[0], os.path.join(od, stem + '.png'))
+            picture = self._overlay(overlay_frame_u8[None], u8, u8.device)
+            if self.overlay_encode == 'device':
+                (data,) = self._files_to_host(*self._encode([0], picture)[1:])
+                with open(os.path.join(od, stem + '.png'), 'wb') as f:
+                    f.write(data)
+            else:
+                save_rgb(picture.cpu().numpy()[0], os.path.join(od, stem + '.png'))
 
     def close(self):
         n = sum(f.result() for f in self.pending)

@@ -1688,25 +1688,39 @@ def overlay_u8(frames_u8, labels_u8, palette, alpha=0.4):
     return out
 
 
-def png_encode_u8(maps_u8, palette768=None, blob=None):
-    """swem_png_encode_u8: (T,H,W) uint8 index maps on the device -> (blob, offsets), both on the device: T complete PNG files
-    back to back, file t = blob[offsets[t]:offsets[t + 1]] (offsets: T + 1 int64).  palette768: 256x3 RGB -> palette PNGs;
-    None -> grayscale (utils/visualization.py:40-43 either way).  blob: a uint8 device buffer of at least
-    T * swem_png_capacity(H, W) bytes to write into (default: a new one).  Nothing here waits for the device: copy `offsets`,
-    then blob[:offsets[T]]."""
-    _chk_u8(maps_u8, 'png_encode_u8', 3)
-    T, H, W = maps_u8.shape
-    cap = _lib.query('swem_png_capacity', H, W)
+PNG_CODES = {'fixed': 0, 'dynamic': 1}       # SWEM_PNG_CODES_* of include/swem_hip_io.h
+
+
+def png_encode_u8(maps_u8, palette768=None, blob=None, codes='fixed'):
+    """swem_png_encode_u8 / swem_png_encode_px_u8: (T,H,W) uint8 index maps or (T,H,W,3) uint8 RGB pictures on the device ->
+    (blob, offsets), both on the device: T complete PNG files back to back, file t = blob[offsets[t]:offsets[t + 1]] (offsets:
+    T + 1 int64).  palette768: 256x3 RGB -> palette PNGs; None -> grayscale (utils/visualization.py:40-43 either way); the 4-d
+    form writes colour type 2 and takes no palette.  codes: 'fixed' -- the fixed Huffman codes; 'dynamic' -- a table of each
+    segment's own where that is smaller.  blob: a uint8 device buffer of at least T * io.png_capacity(H, W, channels) bytes to
+    write into (default: a new one).  Nothing here waits for the device: copy `offsets`, then blob[:offsets[T]]."""
+    if codes not in PNG_CODES:
+        raise ValueError("png_encode_u8: codes is 'fixed' or 'dynamic', got %r" % (codes,))
+    channels = 3 if maps_u8.dim() == 4 else 1
+    _chk_u8(maps_u8, 'png_encode_u8', 4 if channels == 3 else 3)
+    T, H, W = maps_u8.shape[:3]
+    if channels == 3 and (maps_u8.shape[3] != 3 or palette768 is not None):
+        raise _lib.SwemHipError('png_encode_u8: pictures are (T,H,W,3) and take no palette, got %s' % (tuple(maps_u8.shape),))
+    px = channels == 3 or codes != 'fixed'         # the default call stays on the first entry point
+    cap = _lib.query('swem_png_capacity_px', H, W, channels) if px else _lib.query('swem_png_capacity', H, W)
     if blob is None:
         blob = torch.empty(max(T * cap, 1), dtype=torch.uint8, device=maps_u8.device)
     elif _chk_u8(blob, 'png_encode_u8 blob', 1).device != maps_u8.device:
         raise _lib.SwemHipError('png_encode_u8: blob and maps on one device')
     offsets = torch.empty(T + 1, dtype=torch.int64, device=maps_u8.device)
-    nbytes = _lib.query('swem_png_workspace', T, H, W)
+    nbytes = _lib.query('swem_png_workspace_px', T, H, W, channels) if px else _lib.query('swem_png_workspace', T, H, W)
     ws = workspace(nbytes, maps_u8.device)
     pal = None if palette768 is None else _table_bytes(palette768, 768, 'png_encode_u8')
-    _lib.call('swem_png_encode_u8', _stream(), maps_u8.data_ptr(), pal, blob.data_ptr(), blob.numel(), offsets.data_ptr(),
-              T, H, W, ws.data_ptr(), nbytes)
+    if px:
+        _lib.call('swem_png_encode_px_u8', _stream(), maps_u8.data_ptr(), channels, pal, PNG_CODES[codes], blob.data_ptr(),
+                  blob.numel(), offsets.data_ptr(), T, H, W, ws.data_ptr(), nbytes)
+    else:
+        _lib.call('swem_png_encode_u8', _stream(), maps_u8.data_ptr(), pal, blob.data_ptr(), blob.numel(), offsets.data_ptr(),
+                  T, H, W, ws.data_ptr(), nbytes)
     return blob, offsets
 
 
