@@ -1,6 +1,6 @@
 /*
  * swem_hip_io.h -- C ABI of libswem_hip.so, evaluation staging part: decoded bytes in, result bytes out (csrc/stage.hip), result
- * PNG files out (csrc/png.hip).
+ * PNG files out (csrc/png.hip), PNG files in (csrc/png_decode.hip).
  * Conventions, error codes and swem_last_error(): swem_hip.h.
  *
  * The reference's evaluation loop does this work on the host, a frame at a time: its dataset classes turn every decoded JPEG
@@ -115,6 +115,67 @@ size_t swem_png_workspace_px(int T, int H, int W, int channels);
 int swem_png_encode_px_u8(void *stream, const unsigned char *pixels, int channels, const unsigned char *palette768, int codes,
                           unsigned char *blob, size_t blob_bytes, long long *offsets, int T, int H, int W, void *ws,
                           size_t ws_bytes);
+
+/* The way back (csrc/png_decode.hip, csrc/inflate_core.h): T PNG files in, T pixel slots out -- the
+ * annotations of datasets/DAVIS_Test.py:40-49 and datasets/YTVOS_Test.py:116-132 and the palette file of VAL.DAVIS_PALETTE_DIR,
+ * which the reference opens with PIL on the host.  One wavefront per file, all files in one launch: the chunks are walked and
+ * their CRC-32 checked, the IDAT payloads compacted, the zlib stream inflated (stored, fixed and dynamic blocks, distances up to
+ * 32768), the Adler-32 checked, the scanlines unfiltered (types 0-4) and depths 1, 2 and 4 unpacked, most significant bits first.
+ * Reads: no interlace; colour type 3 and 0 at depths 1, 2, 4, 8 (channels 1: the samples as stored, nothing is scaled), colour
+ * type 2 at depth 8 (channels 3).  As strict as tests/png_ref.py and zlib's inflate; a file it refuses gets a status word, an
+ * all-zero slot and sizes (0, 0), and its neighbours are decoded.  0 is a good file. */
+#define SWEM_PNG_ST_OK 0
+#define SWEM_PNG_ST_OFFSETS 1         /* offsets[t] > offsets[t + 1], outside 0..blob_bytes, or a file of 2 GiB and more */
+#define SWEM_PNG_ST_SIGNATURE 2
+#define SWEM_PNG_ST_CHUNK 3           /* a chunk runs past the file */
+#define SWEM_PNG_ST_CRC 4
+#define SWEM_PNG_ST_IHDR 5            /* not first, not once, not 13 bytes */
+#define SWEM_PNG_ST_DIMENSIONS 6      /* zero, or past 2^31 - 1 */
+#define SWEM_PNG_ST_UNSUPPORTED 7     /* a depth, colour type or interlace this decoder does not read; the other `channels` */
+#define SWEM_PNG_ST_METHOD 8          /* compression or filter method not 0 */
+#define SWEM_PNG_ST_PLTE 9            /* missing, late, doubled, of a bad length; present without colour type 3 */
+#define SWEM_PNG_ST_IDAT 10           /* absent, or not consecutive */
+#define SWEM_PNG_ST_CRITICAL 11       /* an unknown critical chunk */
+#define SWEM_PNG_ST_IEND 12           /* missing, or not empty */
+#define SWEM_PNG_ST_TRAILING 13       /* bytes after IEND */
+#define SWEM_PNG_ST_TOO_LARGE 14      /* larger than the slot */
+#define SWEM_PNG_ST_ZLIB_CM 15
+#define SWEM_PNG_ST_ZLIB_CINFO 16
+#define SWEM_PNG_ST_ZLIB_FCHECK 17
+#define SWEM_PNG_ST_ZLIB_FDICT 18
+#define SWEM_PNG_ST_BLOCK_TYPE 19     /* block type 3 */
+#define SWEM_PNG_ST_STORED_LEN 20     /* LEN != ~NLEN */
+#define SWEM_PNG_ST_HLIT_HDIST 21     /* more than 286 literal/length or 30 distance codes */
+#define SWEM_PNG_ST_REPEAT 22         /* a repeat with nothing before it, or past the last length */
+#define SWEM_PNG_ST_OVERSUBSCRIBED 23
+#define SWEM_PNG_ST_INCOMPLETE 24     /* (an empty set and a single code of one bit are legal) */
+#define SWEM_PNG_ST_NO_EOB 25         /* no code for symbol 256 */
+#define SWEM_PNG_ST_BAD_SYMBOL 26     /* symbol 286 or 287, distance symbol 30 or 31, a code that no symbol has */
+#define SWEM_PNG_ST_DISTANCE 27       /* a distance reaching before the start of the output */
+#define SWEM_PNG_ST_NO_FINAL 28       /* the stream ends before the final block */
+#define SWEM_PNG_ST_TRUNCATED 29      /* input running past the IDAT data */
+#define SWEM_PNG_ST_IDAT_LEFT 30      /* IDAT bytes after the Adler-32 */
+#define SWEM_PNG_ST_LENGTH 31         /* inflated length != h * (rowbytes + 1); a longer stream is cut off there */
+#define SWEM_PNG_ST_ADLER 32
+#define SWEM_PNG_ST_FILTER 33         /* a filter byte past 4 */
+#define SWEM_PNG_ST_INDEX 34          /* an index beyond the PLTE entries */
+/* The scratch of one call: the compacted IDAT streams (blob_bytes, rounded up to 16) and T times the inflated scanlines of a full
+ * slot, Hs * (channels * Ws + 1) bytes rounded up to 16.  0 for what the call refuses: T outside 1..65535, Hs or Ws < 1,
+ * channels not 1 or 3, channels * Ws + 1 > 65535, Hs * (channels * Ws + 1) >= 2^31, blob_bytes == 0. */
+size_t swem_png_decode_workspace(int T, int Hs, int Ws, int channels, size_t blob_bytes);
+/*   blob, offsets : as swem_png_encode_* leave them, both on the device: file t = blob[offsets[t] .. offsets[t + 1]); offsets:
+ *                   T + 1 int64, 8-byte aligned.  The kernel checks them against blob_bytes (SWEM_PNG_ST_OFFSETS).
+ *   pixels        : [T][Hs][Ws][channels] uint8 (device); a file of h x w <= Hs x Ws fills the top-left corner, the rest is zero
+ *   sizes         : [T][2] int32 (h, w)                     status : [T] int32 (SWEM_PNG_ST_*)
+ *   palettes      : [T][768] uint8, the PLTE entries and zeros behind them (all zero without a PLTE), or NULL
+ *   n_palette     : [T] int32, the number of PLTE entries, or NULL
+ *   ws            : swem_png_decode_workspace(...) bytes, 16-byte aligned
+ * One launch; the kernel declares about 77 KiB of LDS (a 64 KiB ring of inflated bytes, the code tables).  Refused before any HIP
+ * call: null pointers, a misaligned ws / offsets / sizes / status, channels not 1 or 3, the shapes above (SWEM_E_SHAPE), a short
+ * workspace (SWEM_E_WORKSPACE).  Nothing a file contains makes the kernel read or write outside blob, pixels and ws. */
+int swem_png_decode_u8(void *stream, const unsigned char *blob, size_t blob_bytes, const long long *offsets, int T, int Hs, int Ws,
+                       int channels, unsigned char *pixels, int *sizes, unsigned char *palettes, int *n_palette, int *status,
+                       void *ws, size_t ws_bytes);
 
 #ifdef __cplusplus
 }

@@ -149,6 +149,8 @@ SIGNATURES = {
     'swem_png_capacity_px': (_sz, [_i, _i, _i]),
     'swem_png_workspace_px': (_sz, [_i, _i, _i, _i]),
     'swem_png_encode_px_u8': (_i, [_p, _p, _i, _p, _i, _p, _sz, _p, _i, _i, _i, _p, _sz]),
+    'swem_png_decode_workspace': (_sz, [_i, _i, _i, _i, _sz]),
+    'swem_png_decode_u8': (_i, [_p, _p, _sz, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _sz]),
 }
 
 _lib = None

@@ -8,7 +8,8 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libswem_hip.so')
 # (conv_presplit.hip first: its five minutes are the critical path of a full build)
 SOURCES = ['conv_presplit.hip', 'api.hip', 'conv.hip', 'conv_f32.hip', 'conv_t256.hip', 'bneck.hip', 'pointwise.hip', 'em.hip',
-           'match.hip', 'train.hip', 'lovasz.hip', 'train_conv.hip', 'metrics.hip', 'augment.hip', 'synth.hip', 'stage.hip', 'png.hip']
+           'match.hip', 'train.hip', 'lovasz.hip', 'train_conv.hip', 'metrics.hip', 'augment.hip', 'synth.hip', 'stage.hip', 'png.hip',
+           'png_decode.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 

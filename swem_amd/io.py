@@ -14,6 +14,9 @@ utils/visualization.py:40-43).
 * ``IndexMapWriter(encode='device')`` encodes the palette PNGs on the device too (csrc/png.hip): the bytes
   that cross to the host are the files' bytes, and the thread pool only writes them out.  ``codes='dynamic'`` gives every segment
   a Huffman table of its own; ``overlay_encode='device'`` encodes the overlay pictures there as well (truecolour).
+* ``png_decode`` / ``read_palette``: PNG files -- annotations, stage-0 masks, the palette file -- decoded on the device
+  (csrc/png_decode.hip): the files' bytes are uploaded, inflate, unfilter and unpack run there, and the maps
+  feed ``davis_sequence_u8``, ``metrics.JFMeter`` and ``augment.ClipAugmenter`` without the host touching a pixel.
 Nothing here touches the model.
 """
 import os
@@ -203,6 +206,73 @@ def png_capacity(H, W, channels=1):
     if channels == 1:
         return int(_lib.query('swem_png_capacity', int(H), int(W)))
     return int(_lib.query('swem_png_capacity_px', int(H), int(W), int(channels)))
+
+
+# SWEM_PNG_ST_* of include/swem_hip_io.h: the per-file status words of `png_decode`, by value
+PNG_STATUS = ('OK', 'OFFSETS', 'SIGNATURE', 'CHUNK', 'CRC', 'IHDR', 'DIMENSIONS', 'UNSUPPORTED', 'METHOD', 'PLTE', 'IDAT', 'CRITICAL',
+              'IEND', 'TRAILING', 'TOO_LARGE', 'ZLIB_CM', 'ZLIB_CINFO', 'ZLIB_FCHECK', 'ZLIB_FDICT', 'BLOCK_TYPE', 'STORED_LEN',
+              'HLIT_HDIST', 'REPEAT', 'OVERSUBSCRIBED', 'INCOMPLETE', 'NO_EOB', 'BAD_SYMBOL', 'DISTANCE', 'NO_FINAL', 'TRUNCATED',
+              'IDAT_LEFT', 'LENGTH', 'ADLER', 'FILTER', 'INDEX')
+
+
+class PngDecodeError(ValueError):
+    """`png_decode(check=True)` refused a file: `index` is its place in the list, `status` the word, `name` its name."""
+
+    def __init__(self, index, status):
+        self.index, self.status = int(index), int(status)
+        self.name = PNG_STATUS[self.status] if 0 <= self.status < len(PNG_STATUS) else 'UNKNOWN'
+        ValueError.__init__(self, 'png_decode: file %d refused: SWEM_PNG_ST_%s (%d)' % (self.index, self.name, self.status))
+
+
+def _file_bytes(f):
+    if isinstance(f, (bytes, bytearray, memoryview)):
+        return bytes(f)
+    with open(f, 'rb') as fp:
+        return fp.read()
+
+
+def png_decode(files, slot_hw=None, channels=1, device=None, check=True):
+    """PNG files -- a list of `bytes` or paths -- decoded on the device (csrc/png_decode.hip): the
+    annotations of DAVIS and YouTube-VOS (palette PNGs), the stage-0 masks (grayscale), overlay pictures (channels=3).  The host
+    concatenates the files and uploads their bytes; inflate, unfilter and unpack run on the device.
+      slot_hw  : every file gets an (Hs, Ws) slot; None: the largest height and width among the files' IHDR fields (8 bytes a
+                 file are read here; the kernel stays the authority on the header).  A file whose fields are 0 or past 65535
+                 takes no part in the sizing -- with none left the slot is 1 x 1 -- and is then refused by the kernel
+                 (DIMENSIONS, TOO_LARGE).
+      channels : 1 for palette and grayscale files, 3 for truecolour; a file of the other kind is not sorted out here: the
+                 kernel refuses it as UNSUPPORTED
+      check    : True -- copy the status words back and raise `PngDecodeError` for the first refused file; False -- nothing waits
+    Returns (pixels (T,Hs,Ws) or (T,Hs,Ws,3) uint8, sizes (T,2) int32, palettes (T,768) uint8, n_palette (T,) int32, status (T,)
+    int32), all on the device.  pixels[t] feeds `metrics.JFMeter.add`, `davis_sequence_u8` and `augment.ClipAugmenter` as it is."""
+    if channels not in (1, 3):
+        raise ValueError('png_decode: channels is 1 or 3, got %r' % (channels,))
+    data = [_file_bytes(f) for f in files]
+    if not data:
+        raise ValueError('png_decode: an empty list of files')
+    if slot_hw is None:
+        dims = [(int.from_bytes(d[20:24], 'big'), int.from_bytes(d[16:20], 'big')) for d in data if len(d) >= 24]
+        slot_hw = (max([1] + [h for h, w in dims if 0 < h < 1 << 16 and 0 < w < 1 << 16]),
+                   max([1] + [w for h, w in dims if 0 < h < 1 << 16 and 0 < w < 1 << 16]))
+    offs = np.zeros(len(data) + 1, np.int64)
+    np.cumsum([len(d) for d in data], out=offs[1:])
+    blob = _device_u8(np.frombuffer(bytearray(b''.join(data) or b'\0'), np.uint8), device)
+    offsets = torch.from_numpy(offs).to(blob.device, non_blocking=True)
+    out = ops.png_decode_u8(blob, offsets, slot_hw, channels, want_palette=True)
+    if check:
+        status = out[4].cpu().numpy()
+        bad = np.nonzero(status)[0]
+        if bad.size:
+            raise PngDecodeError(bad[0], status[bad[0]])
+    return out
+
+
+def read_palette(file):
+    """The 768-byte palette of a palette PNG, zero-padded (numpy uint8): what VAL.DAVIS_PALETTE_DIR is read for."""
+    data = _file_bytes(file)
+    pal, n = png_decode([data])[2:4]
+    if int(n[0]) < 1:
+        raise ValueError('read_palette: the file carries no PLTE')
+    return pal[0].cpu().numpy()
 
 
 class IndexMapWriter:

@@ -1724,6 +1724,35 @@ def png_encode_u8(maps_u8, palette768=None, blob=None, codes='fixed'):
     return blob, offsets
 
 
+def png_decode_u8(blob, offsets, slot_hw, channels=1, want_palette=False):
+    """swem_png_decode_u8: T PNG files back to back in `blob` (uint8, device), file t = blob[offsets[t]:offsets[t + 1]] (offsets:
+    T + 1 int64 on the device -- what `png_encode_u8` returns goes straight in) -> (pixels, sizes, palettes, n_palette, status),
+    all on the device: pixels (T,Hs,Ws) uint8 for channels=1 (palette and grayscale files at depths 1, 2, 4, 8, the samples as
+    stored) or (T,Hs,Ws,3) for channels=3 (truecolour); a file of h x w fills the top-left corner of its slot, the rest is zero;
+    sizes (T,2) int32; palettes (T,768) uint8 and n_palette (T,) int32 with want_palette, else None; status (T,) int32, 0 for a
+    good file, io.PNG_STATUS names the others (such a file leaves a zero slot).  Nothing here waits for the device."""
+    _chk_u8(blob, 'png_decode_u8 blob', 1)
+    if not (offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.dim() == 1 and
+            offsets.numel() >= 2 and offsets.device == blob.device):
+        raise _lib.SwemHipError('png_decode_u8: offsets are T + 1 contiguous int64 on the blob\'s device')
+    T = offsets.numel() - 1
+    Hs, Ws = int(slot_hw[0]), int(slot_hw[1])
+    if channels not in (1, 3):
+        raise ValueError('png_decode_u8: channels is 1 or 3, got %r' % (channels,))
+    dev = blob.device
+    pixels = torch.empty((T, Hs, Ws, 3) if channels == 3 else (T, Hs, Ws), dtype=torch.uint8, device=dev)
+    sizes = torch.empty((T, 2), dtype=torch.int32, device=dev)
+    status = torch.empty(T, dtype=torch.int32, device=dev)
+    palettes = torch.empty((T, 768), dtype=torch.uint8, device=dev) if want_palette else None
+    n_palette = torch.empty(T, dtype=torch.int32, device=dev) if want_palette else None
+    nbytes = _lib.query('swem_png_decode_workspace', T, Hs, Ws, channels, blob.numel())
+    ws = workspace(nbytes, dev)
+    _lib.call('swem_png_decode_u8', _stream(), blob.data_ptr(), blob.numel(), offsets.data_ptr(), T, Hs, Ws, channels,
+              pixels.data_ptr(), sizes.data_ptr(), palettes.data_ptr() if want_palette else None,
+              n_palette.data_ptr() if want_palette else None, status.data_ptr(), ws.data_ptr(), nbytes)
+    return pixels, sizes, palettes, n_palette, status
+
+
 def transpose(x, ld=None):
     """(batch, R, Cc) -> (batch, Cc, ld) with zero padded columns."""
     _chk(x)
